@@ -9,8 +9,18 @@ in HBM, as one launch of the fused HIP kernel sml_quantize_pack (K1) per GPU.
 Exponents are the loopback's (the dummy backend returns them unchanged, so
 the local exponent is the global one: W = 1).
 
-Every N (1 by default; `--gpus N` starts the N ranks itself when WORLD_SIZE
-is unset, or they come from torch.distributed.run) reports the SAME two
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline
+needs and no more: it fills the buckets, settles and warms up, times the K
+steps and prints the line (`value`, `ms_per_step` = milliseconds per timed
+step, the headline's roofline from the same timed region).  `--dump-outputs
+DIR` also writes the planes the last timed step left (dump_outputs).
+Everything below that is not the weak_256MiB headline itself — its self-check
+against the committed digests, the strong_1GiB reading, the side fields, the
+CPU baseline, rccl_collnet, and at N > 1 the switch paths and the plugin —
+runs under `--full` only; without it those fields are absent or null.
+
+With --full, every N (1 by default; `--gpus N` starts the N ranks itself when
+WORLD_SIZE is unset, or they come from torch.distributed.run) reports the SAME two
 readings, each with its own timed region, self-check and roofline, so a
 1/2/4/8 curve compares each reading with itself:
   value = weak_256MiB_value   the step is K1 over a 256 MiB bucket (configs[2]'s
@@ -113,7 +123,19 @@ def parse(argv=None):
                          "run by rank 0 in fresh child processes at the end)")
     ap.add_argument("--graph-steps", type=int, default=1,
                     help="capture this many steps per hipGraph replay (1 = eager launches)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run everything else the benchmark measures and checks: the "
+                         "headline's self-check against the committed digests, the strong_1GiB reading, the side "
+                         "fields, the CPU baseline, rccl_collnet and, at N > 1, the switch paths and the plugin "
+                         "(default: a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step computed (rank 0's planes) as "
+                         "DIR/payload.npy (float64: the int32 payload words in host order; a fixed seeded sample "
+                         "of them past 4 Mi words) and DIR/exps.npy (float32: the exponent plane)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(n):
@@ -377,7 +399,7 @@ def main():
     # The headline, `value` = weak_256MiB_value at every N: every GPU runs K1
     # over its own 256 MiB buckets (the metric's bucket; N = 1 is configs[2]'s).
     hl = k1_reading(sw, torch, dist, world, rank, dev, stream, 0, args.numel, P, nb, args.steps, args.warmup,
-                    args.settle_ms, args.graph_steps)
+                    args.settle_ms, args.graph_steps, check=args.full, dump_dir=args.dump_outputs)
     # (the second reading, strong_1GiB_value, runs once the line can be
     # printed without it: below, under the N > 1 watchdog)
     st = None
@@ -385,7 +407,7 @@ def main():
     elapsed, kern_ms_max = hl["elapsed_s"], hl["kernel_ms"]
 
     failures = []
-    if not hl["ok"]:
+    if hl["ok"] is False:
         failures.append(f"self_check ({hl['name']}): " + hl["check_note"])
     diag_failures = []          # diagnostic fields: reported, not fatal (module docstring)
     side, fields, extra = {}, {}, {}
@@ -442,6 +464,7 @@ def main():
             "warmup": args.warmup,
             "settle_ms": args.settle_ms,
             "ms_per_step": round(ms_per_step, 5),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -491,6 +514,9 @@ def main():
         if rehearse:
             line["rehearsal_note"] = ("value / weak_256MiB_value / strong_1GiB_value: " + REHEARSAL_NOTE)
         line.update(fields)
+        if args.dump_outputs:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "files": ["payload.npy", "exps.npy"],
+                                    "what": "rank 0's planes of the last timed step (dump_outputs)"}
         if side:
             line["side"] = side
         if extra:
@@ -521,7 +547,7 @@ def main():
             diag_failures.append(f"side.{key}: {side[key]['error']}")
 
     watchdog = None
-    if world > 1:
+    if world > 1 and args.full:
         # The multi-GPU phase (the strong reading, side fields, switch paths,
         # plugin over the in-node switch) is where a hang could happen; past the deadline the
         # run reports what it has, with the timeout, and every rank exits
@@ -549,32 +575,32 @@ def main():
     # on one GPU), its own timed region, self-check and roofline.  At N > 1 it
     # runs under the watchdog: a hang in its barriers cannot swallow the
     # headline measured above.
-    if args.job_numel:
+    if args.full and args.job_numel:
         st = k1_reading(sw, torch, dist, world, rank, dev, stream, args.job_numel, 0, P, nb, args.strong_steps,
                         args.strong_warmup, args.settle_ms, 1)
         if not st["ok"]:
             failures.append(f"self_check ({st['name']}): " + st["check_note"])
-    if world == 1 and not args.no_side:
+    if world == 1 and args.full and not args.no_side:
         if nb > 1:
             guarded("resident", lambda: bucket_measure(sw, torch, args.numel, P, stream, nbuf=1))
         else:
             guarded("cold_hbm", lambda: bucket_measure(sw, torch, args.numel, P, stream, nbuf=4))
         guarded("copy_ceiling", lambda: copy_ceiling(sw, torch, args.numel, stream, nbuf=nb, k1_ms=kern_ms_max))
-    if world > 1 and not args.no_side:
+    if world > 1 and args.full and not args.no_side:
         if rank == 0:
             # what the peer-to-peer paths rely on: every pair of the node's GPUs can map each other
             guarded("topology", lambda: {
                 "devices": ndev, "name": torch.cuda.get_device_name(dev),
                 "peer_access": [[i == j or torch.cuda.can_device_access_peer(i, j) for j in range(ndev)]
                                 for i in range(ndev)]})
-    if world > 1 and os.environ.get("SML_BENCH_INJECT", "") == f"die:{rank}":
+    if world > 1 and args.full and os.environ.get("SML_BENCH_INJECT", "") == f"die:{rank}":
         # tests only: this rank dies at the start of the diagnostic phase, as
         # one that faults on its first peer access would (the launcher then
         # SIGTERMs the others: term_guard)
         sys.stderr.write(f"[bench rank {rank}] SML_BENCH_INJECT: dying\n")
         sys.stderr.flush()
         os._exit(7)
-    if world > 1 and args.switch_numel:
+    if world > 1 and args.full and args.switch_numel:
         try:
             fields.update(exchange_measure(sw, torch, dist, args.switch_numel, P, world, rank, dev,
                                            rehearsal=pg["rehearsal"]))
@@ -583,7 +609,7 @@ def main():
         fatal, diag = switch_verdicts(fields, lenient=args.lenient_switch)
         failures.extend(fatal)
         diag_failures.extend(diag)
-    if world > 1 and not args.no_plugin:
+    if world > 1 and args.full and not args.no_plugin:
         # configs[4] on every GPU at once: each rank hands the ResNet-50 buckets
         # to its own plugin instance, on an N-rank communicator whose backend
         # is the in-node switch (a real cross-rank SwitchML all-reduce)
@@ -604,7 +630,7 @@ def main():
         extra.update(extra_measurements(sw, torch, torch.randn(args.numel, device=dev, generator=gen), P, stream))
     if world > 1:
         dist.destroy_process_group()
-    if not args.no_rccl_collnet and rank == 0:
+    if args.full and not args.no_rccl_collnet and rank == 0:
         # RCCL itself calling the plugin's CollNet table, in fresh processes
         # (their own RCCL communicator and xgmi session); not part of the
         # headline, and its failure is reported in the field, not fatal
@@ -612,7 +638,7 @@ def main():
         fields["rccl_collnet"] = rccl_collnet_field(world, same_gpu=world == 1 or rehearse)
         if not fields["rccl_collnet"].get("ok", False):
             diag_failures.append("rccl_collnet: " + fields["rccl_collnet"].get("error", "not ok"))
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             side_cpu["cpu_baseline"] = cpu_baseline(N, P, args.cpu_seconds)
         except Exception as e:  # noqa: BLE001 - reported; the headline stands
@@ -653,7 +679,7 @@ REHEARSAL_NOTE = ("rehearsal: the ranks share ONE GPU (SML_BENCH_REHEARSE), so t
 
 
 def k1_reading(sw, torch, dist, world, rank, dev, stream, job_numel, numel, P, nb, steps, warmup, settle_ms,
-               graph_steps=1):
+               graph_steps=1, check=True, dump_dir=None):
     """One timed K1 reading on every rank.
 
     job_numel = 0: every rank quantizes its own `numel`-element buckets (the
@@ -670,7 +696,13 @@ def k1_reading(sw, torch, dist, world, rank, dev, stream, job_numel, numel, P, n
     barrier and a device sync on both sides (wall clock -> value; MAX over
     ranks) and by two HIP events on the launch stream itself (-> average
     launch duration for the roofline; includes the inter-launch gaps, so it
-    is conservative against rocprofv3's per-dispatch durations)."""
+    is conservative against rocprofv3's per-dispatch durations).
+
+    check = False leaves the planes unhashed (a plain run; `ok` is None).
+    dump_dir: rank 0 writes the planes of the LAST timed step there
+    (dump_outputs).  The bucket cycle restarts at bucket 0 after the
+    time-bounded settle launches, so which bucket the last step wrote depends
+    on the arguments alone."""
     off = 0
     if job_numel:
         off, N = sw.fifo_slice(job_numel, world, rank)
@@ -714,6 +746,7 @@ def k1_reading(sw, torch, dist, world, rank, dev, stream, job_numel, numel, P, n
         step, per_call = graph.replay, graph_steps
 
     settle(step, settle_ms)
+    cyc[0] = 0
     for _ in range(warmup // per_call):
         step()
     torch.cuda.synchronize()
@@ -752,8 +785,15 @@ def k1_reading(sw, torch, dist, world, rank, dev, stream, job_numel, numel, P, n
 
     # self-check: the planes the TIMED launches left (the last launch on each
     # bucket, the kernel instance and knobs of this run) against the oracle's digests
-    want = expected_digests(job_numel, world, rank, N, P, nb)
-    if want is None:
+    if dump_dir and rank == 0:
+        last = (cyc[0] - 1) % nb if graph_steps <= 1 else nb - 1
+        dump_outputs(torch, dump_dir, pls[last], exs[last], N)
+    want = expected_digests(job_numel, world, rank, N, P, nb) if check else None
+    if not check:
+        ok, checked = None, 0
+        check_note = ("not checked: a plain run only times the steps (--full compares the timed planes with "
+                      "tests/golden/digests_bench.json)")
+    elif want is None:
         ok, check_note, checked = True, "no committed digest for this shape: not checked", 0
     else:
         got = [planes_sha256(torch, exs[b], pls[b], N, P) for b in range(nb)]
@@ -761,14 +801,40 @@ def k1_reading(sw, torch, dist, world, rank, dev, stream, job_numel, numel, P, n
         ok, checked = not bad, nb
         check_note = ("timed exponent + BE payload planes of every bucket == tests/golden/digests_bench.json"
                       if ok else f"buckets {bad} differ from tests/golden/digests_bench.json")
-    ok_t = torch.tensor([int(ok), checked], dtype=torch.int32, device=dev)
-    if world > 1:
-        dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
+    if check:
+        ok_t = torch.tensor([int(ok), checked], dtype=torch.int32, device=dev)
+        if world > 1:
+            dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
+        ok, checked = bool(ok_t[0].item()), int(ok_t[1].item())
     del xs, pls, exs, launchers
     return {"name": "strong_1GiB" if job_numel else "weak_256MiB", "job_numel": job_numel or world * N,
             "numel_per_gpu": N, "num_blocks_per_gpu": B, "alg_bytes_per_gpu": 8 * N + B, "total_alg": total_alg,
             "steps": steps, "warmup": warmup, "elapsed_s": elapsed, "kernel_ms": kern_ms_max,
-            "ok": bool(ok_t[0].item()), "checked": int(ok_t[1].item()), "check_note": check_note}
+            "ok": ok, "checked": checked, "check_note": check_note}
+
+
+DUMP_SEED = 20260   # the sample of payload words --dump-outputs keeps (fixed: two builds keep the same words)
+DUMP_MAX_WORDS = 1 << 22
+
+
+def dump_outputs(torch, dump_dir, payload, exps, numel):
+    """--dump-outputs: the planes a caller of the timed path receives from
+    its last step, as .npy files two builds can be compared by.
+      payload.npy  float64 (exact for int32): the first `numel` payload words
+                   in host order (the wire words are big-endian), all of them
+                   up to 4 Mi words, past that a fixed seeded sample of 4 Mi
+                   word positions in ascending order (32 MiB)
+      exps.npy     float32: the whole int8 exponent plane (one per packet)"""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    if numel > DUMP_MAX_WORDS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, numel, DUMP_MAX_WORDS))
+        words = payload[torch.from_numpy(idx).to(payload.device)]
+    else:
+        words = payload[:numel]
+    be = words.cpu().numpy().view(">i4")
+    np.save(os.path.join(dump_dir, "payload.npy"), be.astype(np.float64))
+    np.save(os.path.join(dump_dir, "exps.npy"), exps.cpu().numpy().astype(np.float32))
 
 
 def reading_block(r, world, nb, P, scaling):

@@ -18,7 +18,7 @@ step() { "$@"; rc=$?; case $rc in 124|137|134|139) echo "step failed rc=$rc: $*"
 # collect_pmc.py also reports the average over the timed window alone.  The
 # strong_1GiB reading runs too (its own grid: collect_pmc.py reports each
 # grid's launches apart, so the two readings' K1 launches are never mixed).
-KT_ARGS="$ROOT/bench.py --steps 2000 --no-cpu-baseline --no-side --no-rccl-collnet"
+KT_ARGS="$ROOT/bench.py --steps 2000 --full --no-cpu-baseline --no-side --no-rccl-collnet"
 step timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- python3 $KT_ARGS > "$OUT/kt.log" 2>&1
 # PMC passes: bytes per launch do not depend on clocks; few launches suffice
 ARGS="$ROOT/bench.py --steps 20 --warmup 5 --settle-ms 0 --job-numel 0 --no-cpu-baseline --no-side --no-rccl-collnet"

@@ -87,6 +87,31 @@ def test_bench_bucket_on_gpu_hashes_to_digest(cuda):
         assert bench.planes_sha256(torch, ex, pl, N, 256) == d["bucket_T1"][b]
 
 
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs (bench.dump_outputs): payload.npy holds the payload
+    words in HOST order as float64 (exact for int32) — all of them up to
+    DUMP_MAX_WORDS, past that the same seeded sample on every call — never
+    the padding past `numel`; exps.npy the whole exponent plane as float32."""
+    import torch
+    n = 70_001
+    x = O.splitmix_grad(4242, n)
+    q, e = O.quantize(x, 256, 1), O.exponents(x, 256)
+    pl, ex = torch.from_numpy(q.view(np.int32).copy()), torch.from_numpy(e.copy())
+    host = q[:n].view(">i4").astype(np.float64)
+    assert np.abs(host).max() < 2.0 ** 31 and np.abs(host).max() > 2.0 ** 20    # quantized values, not swapped bytes
+    bench.dump_outputs(torch, str(tmp_path / "a"), pl, ex, n)
+    pay, exps = np.load(tmp_path / "a" / "payload.npy"), np.load(tmp_path / "a" / "exps.npy")
+    assert pay.dtype == np.float64 and np.array_equal(pay, host)
+    assert exps.dtype == np.float32 and np.array_equal(exps, e.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_WORDS", 5000)
+    for d in ("b", "c"):
+        bench.dump_outputs(torch, str(tmp_path / d), pl, ex, n)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, 5000))
+    pay = np.load(tmp_path / "b" / "payload.npy")
+    assert pay.shape == (5000,) and np.array_equal(pay, host[idx])
+    assert np.array_equal(pay, np.load(tmp_path / "c" / "payload.npy"))
+
+
 def test_switch_verdicts_wrong_bits_fatal_for_every_path():
     """bench.py's N > 1 switch checks: a path that RAN and is
     not verified fails the run, whichever path it is; a path that could not

@@ -1,6 +1,6 @@
 """The driver's N > 1 bench command, observed by the GPU suite (VERDICT r4
-#2): `bench.py --gpus 2 --steps 4 --warmup 2` as a fresh child process on a
-one-GPU box, under SML_BENCH_REHEARSE=1 — both ranks on cuda:0, each an RCCL
+#2): `bench.py --gpus 2 --steps 4 --warmup 2 --full` as a fresh child process
+on a one-GPU box, under SML_BENCH_REHEARSE=1 — both ranks on cuda:0, each an RCCL
 host of its own, so every collective runs in RCCL's kernels as on a node
 (bench.py main).  The line must parse and carry: n_gpus 2, the nccl (RCCL)
 backend, the headline's self-check against the committed digests, every
@@ -111,7 +111,7 @@ def test_bench_n2_rehearsal_line(cuda, tmp_path, launcher, n):
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")
            and not k.startswith("TORCHELASTIC_")}
     env["SML_BENCH_REHEARSE"] = "1"
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "4", "--warmup", "2"]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "4", "--warmup", "2", "--full"]
     if launcher == "bench":
         cmd = [sys.executable, "-u", *args]
     else:
@@ -143,7 +143,7 @@ def test_bench_n2_rehearsal_line(cuda, tmp_path, launcher, n):
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_bench_n1_line(cuda, tmp_path):
-    """The driver's N = 1 line keeps its contract: the metric and unit of
+    """The driver's N = 1 line under --full keeps its contract: the metric and unit of
     BASELINE.json, the headline's self-check against the committed digests,
     `roofline` (hbm bound, 8 TB/s peak, frac = achieved / peak, PMC traffic
     within 0.1 % of the algorithmic bytes) and `cpu_baseline` (the oracle's
@@ -157,7 +157,7 @@ def test_bench_n1_line(cuda, tmp_path):
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     quick = ["--no-cpu-baseline", "--no-side", "--no-rccl-collnet"]
     for extra in ([], ["--graph-steps", "4"] + quick, ["--buckets", "1"] + quick):
-        cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "4",
+        cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "4", "--full",
                "--cpu-seconds", "2"] + extra
         rc, out, err, wall = run_child(cmd, env, str(tmp_path), 500, "bench.py --gpus 1")
         lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -200,7 +200,7 @@ def test_bench_rehearsal_survives_a_failed_first_contact(cuda, tmp_path):
     env["SML_BENCH_REHEARSE"] = "1"
     env["SML_BENCH_INJECT"] = "xgmi_switch:1"
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--switch-numel", "4194304", "--job-numel", "0", "--no-plugin", "--no-rccl-collnet",
+           "--full", "--switch-numel", "4194304", "--job-numel", "0", "--no-plugin", "--no-rccl-collnet",
            "--exchange-timeout", "150"]
     rc, out, err, wall = run_child(cmd, env, str(tmp_path), 500, "bench.py --gpus 2 (injected xgmi setup failure)")
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -233,8 +233,8 @@ def test_bench_line_survives_a_dead_rank(cuda, tmp_path, dying):
            and not k.startswith("TORCHELASTIC_")}
     env["SML_BENCH_REHEARSE"] = "1"
     env["SML_BENCH_INJECT"] = f"die:{dying}"
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--job-numel", "0",
-            "--switch-numel", "4194304", "--no-rccl-collnet", "--exchange-timeout", "200"]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full",
+            "--job-numel", "0", "--switch-numel", "4194304", "--no-rccl-collnet", "--exchange-timeout", "200"]
     cmd = [sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(rendezvous_port()), *args]
     rc, out, err, wall = run_child(cmd, env, str(tmp_path), 500, f"bench.py --gpus 2 (rank {dying} dies)")
@@ -247,6 +247,54 @@ def test_bench_line_survives_a_dead_rank(cuda, tmp_path, dying):
     assert term, (line.get("diagnostic_failures"), err[-2000:])
     assert ("printed by rank 1" in term[0]) == (dying == 0), term
     assert wall < 150, wall      # SIGTERM answered at once, not after the watchdog or the SIGKILL grace
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_bench_plain_line_and_dumped_outputs(cuda, tmp_path):
+    """A plain run (`--gpus 1 --steps K --warmup W`, no --full) times the
+    headline and nothing else: the line keeps metric / value / unit /
+    higher_is_better / dtype / ms_per_step, `steps` is the K asked for, and
+    every field --full adds is absent or null.  --dump-outputs writes the
+    planes of the LAST timed step — bucket (W + 2 + K - 1) % 4 of the cycle
+    that restarts after the settle launches (k1_reading: 2 untimed passes
+    through the timing code precede the region) — as float64 host-order
+    payload words (here a seeded sample: the bucket is just past 4 Mi words
+    and no multiple of the packet) and the float32 exponent plane, equal bit
+    for bit to the oracle's over the same integer-exact bucket."""
+    import numpy as np
+    from oracle import oracle as O
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        base = json.load(f)
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    n, K, W = 4_200_003, 5, 3
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+           "--numel", str(n), "--dump-outputs", str(dump)]
+    rc, out, err, wall = run_child(cmd, env, str(tmp_path), 250, "bench.py --gpus 1 (plain, --dump-outputs)")
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, (rc, err[-1500:])
+    line = json.loads(lines[0])
+    assert rc == 0, (rc, line.get("failures"), err[-800:])
+    assert line["metric"] == base["metric"] and line["unit"] == "GB/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32->i32" and line["n_gpus"] == 1 and line["full"] is False
+    assert line["steps"] == K and line["warmup"] == W and line["config"]["numel_per_gpu"] == n
+    assert line["value"] == line["weak_256MiB_value"] > 0
+    B = -(-n // 256)
+    assert abs(line["value"] - (8 * n + B) / (line["ms_per_step"] * 1e-3) / 1e9) <= 0.02 * line["value"]
+    assert 0 < line["ms_per_step"] * K / 1e3 < wall
+    assert line["self_check"] is None and line["strong_1GiB_value"] is None
+    for k in ("strong_1GiB", "cpu_baseline", "side", "rccl_collnet", "extra", "failures", "diagnostic_failures"):
+        assert k not in line, k
+    pay, exps = np.load(dump / "payload.npy"), np.load(dump / "exps.npy")
+    assert pay.dtype == np.float64 and exps.dtype == np.float32
+    assert pay.nbytes + exps.nbytes <= 64 << 20
+    x = O.splitmix_grad(bench.BENCH_SEED0 + (W + 2 + K - 1) % 4, n)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_MAX_WORDS))
+    want = O.quantize(x, 256, 1)[idx].view(">i4").astype(np.float64)
+    assert pay.shape == want.shape and np.array_equal(pay, want)
+    assert np.array_equal(exps, O.exponents(x, 256).astype(np.float32))
 
 
 def test_rendezvous_port_is_below_the_ephemeral_range():

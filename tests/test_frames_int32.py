@@ -190,11 +190,16 @@ def test_int32_rx_streams_match_oracle(cuda, P, n, where):
     ref = O.RxStateI32(n, P)
     rx = sw.RxSliceInt32(n, P, device=cuda)
     rx.reset()
+    # the rx calls are asynchronous: each frame buffer lives until the sync (a
+    # pinned block released earlier is handed to the next pin_memory() at once
+    # and overwritten while the first call may still be reading it)
+    held = []
     for lo, hi in ((0, cut), (cut, nfr)):
         part = s[lo * fb:hi * fb]
         O.unpack_frames_i32(part, hi - lo, fb, ref, job_id=7)
         t = torch.from_numpy(part.copy())
         t = t.to(cuda) if where == "device" else t.pin_memory()
+        held.append(t)
         sw.unpack_frames_int32(t, hi - lo, rx, job_id=7)
     torch.cuda.synchronize()
     assert np.array_equal(rx.out.cpu().numpy(), ref.out)
