@@ -648,52 +648,6 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_int32_fixup(RxArgs a, uint
     }
 }
 
-// ------------------------------------------------------------ host side
-
-template <bool ALIGNED, bool GLOBAL, bool I32 = false>
-static void launch_frames_p(uint32_t P, bool nts, dim3 grid, hipStream_t st, const FrameArgs& a) {
-#define SML_FR(PN)                                                                                   \
-    if (nts) k_quantize_frames<PN, ALIGNED, GLOBAL, true, I32><<<grid, kBlockThreads, 0, st>>>(a);   \
-    else k_quantize_frames<PN, ALIGNED, GLOBAL, false, I32><<<grid, kBlockThreads, 0, st>>>(a);
-    switch (P) {
-        case 64:   SML_FR(64) break;
-        case 128:  SML_FR(128) break;
-        case 256:  SML_FR(256) break;
-        case 512:  SML_FR(512) break;
-        default:   SML_FR(1024) break;
-    }
-#undef SML_FR
-}
-
-template <bool NT>
-static void launch_rx_apply_nt(uint32_t P, dim3 grid, hipStream_t st, const RxArgs& a) {
-    switch (P) {
-        case 64:   k_rx_apply<64, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 128:  k_rx_apply<128, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 256:  k_rx_apply<256, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 512:  k_rx_apply<512, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        default:   k_rx_apply<1024, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-    }
-}
-
-// The output of a slice from the non-temporal threshold on takes
-// non-temporal stores, as K4's does (sml_set_payload_nt_threshold).
-static void launch_rx_apply(uint32_t P, dim3 grid, hipStream_t st, const RxArgs& a) {
-    if (4 * a.numel >= g_nt_threshold.load(std::memory_order_relaxed)) launch_rx_apply_nt<true>(P, grid, st, a);
-    else launch_rx_apply_nt<false>(P, grid, st, a);
-}
-
-template <bool NT>
-static void launch_rx_int32_nt(uint32_t P, dim3 grid, hipStream_t st, const RxArgs& a) {
-    switch (P) {
-        case 64:   k_rx_int32<64, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 128:  k_rx_int32<128, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 256:  k_rx_int32<256, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 512:  k_rx_int32<512, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        default:   k_rx_int32<1024, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-    }
-}
-
 }  // namespace sml
 
 using namespace sml;
@@ -762,13 +716,37 @@ static void frame_args(const sml_frame_params* prm, uint64_t numel, uint32_t P, 
 // the threshold on (written once, handed on); host frames (a NIC's pinned
 // mbufs) keep the default policy.
 static bool frames_nt(const void* frames, uint64_t bytes) {
-    if (bytes < g_nt_threshold.load(std::memory_order_relaxed)) return false;
+    if (!nt_from(bytes)) return false;
     hipPointerAttribute_t pa;
     if (hipPointerGetAttributes(&pa, frames) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
     return pa.type == hipMemoryTypeDevice;
+}
+
+// The frame set of every frame entry point: present, 4-byte aligned, frames
+// of P elements at a 4-byte multiple stride.
+static sml_status_t check_frames(const void* frames, uint64_t stride, uint32_t P) {
+    if (!frames) return SML_ERR_INVALID_ARG;
+    if (!aligned4(frames) || stride % 4 || stride < sml_frame_bytes(P)) return SML_ERR_ALIGNMENT;
+    return SML_OK;
+}
+
+// The fields the two receive entry points share; b, exps, out, W and xcd are
+// the caller's.
+static RxArgs rx_args(const void* frames, uint64_t num_frames, uint64_t stride, uint64_t numel, uint32_t P,
+                      uint64_t job_id, uint64_t* d_state, uint64_t* d_counts) {
+    RxArgs a;
+    a.frames = static_cast<const uint8_t*>(frames);
+    a.nframes = num_frames;
+    a.stride = stride;
+    a.numel = numel;
+    a.nblocks = sml_num_blocks(numel, P);
+    a.state = reinterpret_cast<unsigned long long*>(d_state);
+    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
+    a.job = (uint8_t)job_id;
+    return a;
 }
 
 }  // namespace sml
@@ -781,8 +759,8 @@ sml_status_t sml_quantize_pack_frames(const float* d_in, uint64_t numel, uint32_
     if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
     if (W == 0 || !prm || batch_max == 0) return SML_ERR_INVALID_ARG;
     if (numel == 0) return SML_OK;
-    if (!d_in || !aligned4(d_in) || !frames) return SML_ERR_INVALID_ARG;
-    if (!aligned4(frames) || stride % 4 || stride < sml_frame_bytes(P)) return SML_ERR_ALIGNMENT;
+    if (!d_in || !aligned4(d_in)) return SML_ERR_INVALID_ARG;
+    if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
     FrameArgs a;
     const uint64_t B = sml_num_blocks(numel, P);
     frame_args(prm, numel, P, W, B < batch_max ? B : batch_max, frames, stride, a);
@@ -792,8 +770,11 @@ sml_status_t sml_quantize_pack_frames(const float* d_in, uint64_t numel, uint32_
     hipStream_t st = (hipStream_t)stream;
     const bool al = aligned16(d_in);
     const bool nts = frames_nt(frames, (a.nblocks + a.b) * stride);
-    if (d_global_exps) { if (al) launch_frames_p<true, true>(P, nts, grid, st, a); else launch_frames_p<false, true>(P, nts, grid, st, a); }
-    else               { if (al) launch_frames_p<true, false>(P, nts, grid, st, a); else launch_frames_p<false, false>(P, nts, grid, st, a); }
+    dispatch_packet(P, [&](auto Pc) {
+        dispatch_bools([&](auto AL, auto GLOBAL, auto NTS) {
+            k_quantize_frames<Pc(), AL(), GLOBAL(), NTS(), false><<<grid, kBlockThreads, 0, st>>>(a);
+        }, al, d_global_exps != nullptr, nts);
+    });
     return launch_check();
 }
 
@@ -802,16 +783,20 @@ sml_status_t sml_pack_frames_int32(const int32_t* d_in, uint64_t numel, uint32_t
     if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
     if (!prm) return SML_ERR_INVALID_ARG;
     if (numel == 0) return SML_OK;
-    if (!d_in || !aligned4(d_in) || !frames) return SML_ERR_INVALID_ARG;
-    if (!aligned4(frames) || stride % 4 || stride < sml_frame_bytes(P)) return SML_ERR_ALIGNMENT;
+    if (!d_in || !aligned4(d_in)) return SML_ERR_INVALID_ARG;
+    if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
     FrameArgs a;
     frame_args(prm, numel, P, 1, 0, frames, stride, a);       // INT32: no extra batch
     a.in = reinterpret_cast<const float*>(d_in);              // words moved as bits
     dim3 grid(grid_for_tiles(a.ntiles));
     hipStream_t st = (hipStream_t)stream;
     const bool nts = frames_nt(frames, a.nblocks * stride);
-    if (aligned16(d_in)) launch_frames_p<true, false, true>(P, nts, grid, st, a);
-    else launch_frames_p<false, false, true>(P, nts, grid, st, a);
+    dispatch_packet(P, [&](auto Pc) {
+        dispatch_bools([&](auto AL, auto NTS) {
+            // I32 exists only without global exponents: it has no scale
+            k_quantize_frames<Pc(), AL(), false, NTS(), true><<<grid, kBlockThreads, 0, st>>>(a);
+        }, aligned16(d_in), nts);
+    });
     return launch_check();
 }
 
@@ -823,30 +808,29 @@ sml_status_t sml_dequantize_frames(const void* frames, uint64_t num_frames, uint
     if (W == 0 || batch_max == 0) return SML_ERR_INVALID_ARG;
     if (num_frames == 0) return SML_OK;
     if (num_frames >= 0xFFFFFFFEull) return SML_ERR_UNSUPPORTED;
-    if (!frames || !d_state || (numel && (!d_exps || !d_out))) return SML_ERR_INVALID_ARG;
-    if (!aligned4(frames) || !aligned4(d_out) || stride % 4 || stride < sml_frame_bytes(P)) return SML_ERR_ALIGNMENT;
+    if (!d_state || (numel && (!d_exps || !d_out))) return SML_ERR_INVALID_ARG;
+    if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
+    if (!aligned4(d_out)) return SML_ERR_ALIGNMENT;
     if (((uintptr_t)d_state & 7u) || (d_counts && ((uintptr_t)d_counts & 7u))) return SML_ERR_ALIGNMENT;
-    RxArgs a;
+    RxArgs a = rx_args(frames, num_frames, stride, numel, P, job_id, d_state, d_counts);
     const uint32_t U = (uint32_t)rx_slices((int)P);
-    a.xcd = U < 4 ? g_xcd_chunk.load(std::memory_order_relaxed) * (4 / U)   // XCD runs keep their byte length
-                  : g_xcd_chunk.load(std::memory_order_relaxed);
-    a.frames = static_cast<const uint8_t*>(frames);
-    a.nframes = num_frames;
-    a.stride = stride;
-    a.numel = numel;
-    a.nblocks = sml_num_blocks(numel, P);
+    a.xcd = xcd_chunk_for(U);
     a.b = a.nblocks < batch_max ? a.nblocks : batch_max;
-    a.state = reinterpret_cast<unsigned long long*>(d_state);
     a.exps = d_exps;
     a.out = d_out;
-    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
     a.W = W;
-    a.job = (uint8_t)job_id;
     hipStream_t st = (hipStream_t)stream;
     k_rx_claim<<<grid_for_vec(num_frames), kBlockThreads, 0, st>>>(a);
     const uint64_t tile = (uint64_t)U * kWave * 4;
     const uint64_t ntiles = (a.nblocks * P + tile - 1) / tile;
-    if (ntiles) launch_rx_apply(P, dim3(grid_for_tiles(ntiles)), st, a);
+    if (ntiles) {
+        const dim3 grid(grid_for_tiles(ntiles));
+        // the output takes non-temporal stores from the threshold on, as K4's
+        dispatch_packet(P, [&](auto Pc) {
+            dispatch_bools([&](auto NT) { k_rx_apply<Pc(), NT()><<<grid, kBlockThreads, 0, st>>>(a); },
+                           nt_from(4 * numel));
+        });
+    }
     return launch_check();
 }
 
@@ -856,28 +840,23 @@ sml_status_t sml_unpack_frames_int32(const void* frames, uint64_t num_frames, ui
     if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
     if (num_frames == 0) return SML_OK;
     if (num_frames > kRxI32MaxFrames) return SML_ERR_UNSUPPORTED;
-    if (!frames || !d_state || (numel && !d_out)) return SML_ERR_INVALID_ARG;
-    if (!aligned4(frames) || !aligned4(d_out) || stride % 4 || stride < sml_frame_bytes(P)) return SML_ERR_ALIGNMENT;
+    if (!d_state || (numel && !d_out)) return SML_ERR_INVALID_ARG;
+    if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
+    if (!aligned4(d_out)) return SML_ERR_ALIGNMENT;
     if (((uintptr_t)d_state & 7u) || (d_counts && ((uintptr_t)d_counts & 7u))) return SML_ERR_ALIGNMENT;
-    RxArgs a;
+    RxArgs a = rx_args(frames, num_frames, stride, numel, P, job_id, d_state, d_counts);
     a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
-    a.frames = static_cast<const uint8_t*>(frames);
-    a.nframes = num_frames;
-    a.stride = stride;
-    a.numel = numel;
-    a.nblocks = sml_num_blocks(numel, P);
     a.b = 0;                                                  // INT32: no extra batch
-    a.state = reinterpret_cast<unsigned long long*>(d_state);
     a.exps = nullptr;
     a.out = reinterpret_cast<float*>(d_out);                  // words stored as bits
-    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
     a.W = 1;
-    a.job = (uint8_t)job_id;
     hipStream_t st = (hipStream_t)stream;
     const uint64_t frames_per_tile = (uint64_t)rx_int32_slices((int)P) * kWave * 4 / P;
     const dim3 grid(grid_for_tiles((num_frames + frames_per_tile - 1) / frames_per_tile));
-    if (4 * numel >= g_nt_threshold.load(std::memory_order_relaxed)) launch_rx_int32_nt<true>(P, grid, st, a);
-    else launch_rx_int32_nt<false>(P, grid, st, a);
+    dispatch_packet(P, [&](auto Pc) {
+        dispatch_bools([&](auto NT) { k_rx_int32<Pc(), NT()><<<grid, kBlockThreads, 0, st>>>(a); },
+                       nt_from(4 * numel));
+    });
     // a grid that spreads a call's dirty pkt_ids over the chip; with no
     // conflict its workgroups read two words and end
     k_rx_int32_fixup<<<kRxFixupBlocks, kBlockThreads, 0, st>>>(a, P);

@@ -11,6 +11,7 @@
 #include <atomic>
 
 #include "sml_device.h"
+#include "sml_dispatch.h"
 #include "switchml_hip.h"
 
 namespace sml {
@@ -36,6 +37,15 @@ inline bool valid_packet(uint32_t P) {
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+// The XCD chunk for tiles of U slices: XCD runs keep their byte length
+// (C workgroups of 4 U-slice tiles).  Kernels on 4-slice tiles take the
+// plain g_xcd_chunk.
+inline uint32_t xcd_chunk_for(uint32_t U) { return g_xcd_chunk.load(std::memory_order_relaxed) * (4 / U); }
+
+// Store policy of an output plane of `bytes`: non-temporal from the
+// threshold on (sml_set_payload_nt_threshold).
+inline bool nt_from(uint64_t bytes) { return bytes >= g_nt_threshold.load(std::memory_order_relaxed); }
 
 inline uint32_t grid_for_tiles(uint64_t ntiles) {
     uint64_t g = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;

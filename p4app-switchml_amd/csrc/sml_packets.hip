@@ -442,17 +442,9 @@ sml_status_t sml_preprocess_burst(const sml_packet_burst* burst, void* stream) {
     const dim3 grid((a.count + kWavesPerBlock - 1) / kWavesPerBlock);
     const hipStream_t s = (hipStream_t)stream;
     const bool rne = (a.flags & SML_FLAG_ROUND_RNE) != 0;
-#define SML_PRE(PN)                                                                        \
-    if (rne) k_preprocess_burst<PN, true><<<grid, kBlockThreads, 0, s>>>(a);               \
-    else k_preprocess_burst<PN, false><<<grid, kBlockThreads, 0, s>>>(a);
-    switch (a.packet_numel) {
-        case 64: SML_PRE(64) break;
-        case 128: SML_PRE(128) break;
-        case 256: SML_PRE(256) break;
-        case 512: SML_PRE(512) break;
-        default: SML_PRE(1024) break;
-    }
-#undef SML_PRE
+    dispatch_packet(a.packet_numel, [&](auto Pc) {
+        dispatch_bools([&](auto RNE) { k_preprocess_burst<Pc(), RNE()><<<grid, kBlockThreads, 0, s>>>(a); }, rne);
+    });
     return launch_check();
 }
 
@@ -463,13 +455,7 @@ sml_status_t sml_postprocess_burst(const sml_packet_burst* burst, void* stream) 
     const sml_packet_burst& a = *burst;
     const dim3 grid((a.count + kWavesPerBlock - 1) / kWavesPerBlock);
     const hipStream_t s = (hipStream_t)stream;
-    switch (a.packet_numel) {
-        case 64: k_postprocess_burst<64><<<grid, kBlockThreads, 0, s>>>(a); break;
-        case 128: k_postprocess_burst<128><<<grid, kBlockThreads, 0, s>>>(a); break;
-        case 256: k_postprocess_burst<256><<<grid, kBlockThreads, 0, s>>>(a); break;
-        case 512: k_postprocess_burst<512><<<grid, kBlockThreads, 0, s>>>(a); break;
-        default: k_postprocess_burst<1024><<<grid, kBlockThreads, 0, s>>>(a); break;
-    }
+    dispatch_packet(a.packet_numel, [&](auto Pc) { k_postprocess_burst<Pc()><<<grid, kBlockThreads, 0, s>>>(a); });
     return launch_check();
 }
 
@@ -482,22 +468,11 @@ sml_status_t sml_exchange_burst(const sml_packet_burst* burst, void* stream) {
     const hipStream_t s = (hipStream_t)stream;
     const bool rne = (a.flags & SML_FLAG_ROUND_RNE) != 0;
     const bool proc = (a.flags & SML_FLAG_PROCESS_PACKET) != 0;
-#define SML_XCH(PN)                                                                                \
-    if (proc) {                                                                                    \
-        if (rne) k_exchange_burst<PN, true, true><<<grid, kBlockThreads, 0, s>>>(a);               \
-        else k_exchange_burst<PN, false, true><<<grid, kBlockThreads, 0, s>>>(a);                  \
-    } else {                                                                                       \
-        if (rne) k_exchange_burst<PN, true, false><<<grid, kBlockThreads, 0, s>>>(a);              \
-        else k_exchange_burst<PN, false, false><<<grid, kBlockThreads, 0, s>>>(a);                 \
-    }
-    switch (a.packet_numel) {
-        case 64: SML_XCH(64) break;
-        case 128: SML_XCH(128) break;
-        case 256: SML_XCH(256) break;
-        case 512: SML_XCH(512) break;
-        default: SML_XCH(1024) break;
-    }
-#undef SML_XCH
+    dispatch_packet(a.packet_numel, [&](auto Pc) {
+        dispatch_bools([&](auto RNE, auto PROC) {
+            k_exchange_burst<Pc(), RNE(), PROC()><<<grid, kBlockThreads, 0, s>>>(a);
+        }, rne, proc);
+    });
     return launch_check();
 }
 
@@ -550,17 +525,11 @@ sml_status_t server_launch(sml_burst_server* s) {
     st = sml::hip_check(hipMemsetAsync(s->arrive, 0, sizeof(uint32_t), s->stream));
     if (st != SML_OK) return st;
     const dim3 grid(sml::kServerGroups), block(sml::kServerThreads);
-#define SML_SRV(PN)                                                                                        \
-    if (s->rne) sml::k_burst_server<PN, true><<<grid, block, 0, s->stream>>>(s->dctl, s->arrive, s->idle_ticks); \
-    else sml::k_burst_server<PN, false><<<grid, block, 0, s->stream>>>(s->dctl, s->arrive, s->idle_ticks);
-    switch (s->packet_numel) {
-        case 64: SML_SRV(64) break;
-        case 128: SML_SRV(128) break;
-        case 256: SML_SRV(256) break;
-        case 512: SML_SRV(512) break;
-        default: SML_SRV(1024) break;
-    }
-#undef SML_SRV
+    sml::dispatch_packet(s->packet_numel, [&](auto Pc) {
+        sml::dispatch_bools([&](auto RNE) {
+            sml::k_burst_server<Pc(), RNE()><<<grid, block, 0, s->stream>>>(s->dctl, s->arrive, s->idle_ticks);
+        }, s->rne);
+    });
     st = sml::launch_check();
     s->launched = st == SML_OK;
     s->last_activity = std::chrono::steady_clock::now();

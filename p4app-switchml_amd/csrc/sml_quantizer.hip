@@ -411,39 +411,6 @@ __global__ void k_scale_lut(float* lut, uint32_t W) {
 
 // ------------------------------------------------------------ host side
 
-// Dispatch tables: runtime (P, tile slices U, alignment, mode) -> template
-// instance.  U is 1, 2 or 4 and at least P / 256 (quantize_common).
-template <int P, bool ALIGNED, bool GLOBAL, bool BE, bool RNE>
-static void launch_quant_u(uint32_t U, bool nts, dim3 grid, hipStream_t st, const QuantArgs& a) {
-    if constexpr (P <= 256) {
-        if (U == 1) {
-            if (nts) k_quantize_pack<P, ALIGNED, GLOBAL, BE, RNE, 1, true><<<grid, kBlockThreads, 0, st>>>(a);
-            else k_quantize_pack<P, ALIGNED, GLOBAL, BE, RNE, 1><<<grid, kBlockThreads, 0, st>>>(a);
-            return;
-        }
-    }
-    if constexpr (P <= 512) {
-        if (U == 2) {
-            if (nts) k_quantize_pack<P, ALIGNED, GLOBAL, BE, RNE, 2, true><<<grid, kBlockThreads, 0, st>>>(a);
-            else k_quantize_pack<P, ALIGNED, GLOBAL, BE, RNE, 2><<<grid, kBlockThreads, 0, st>>>(a);
-            return;
-        }
-    }
-    if (nts) { k_quantize_pack<P, ALIGNED, GLOBAL, BE, RNE, 4, true><<<grid, kBlockThreads, 0, st>>>(a); return; }
-    k_quantize_pack<P, ALIGNED, GLOBAL, BE, RNE, 4><<<grid, kBlockThreads, 0, st>>>(a);
-}
-
-template <bool ALIGNED, bool GLOBAL, bool BE, bool RNE>
-static void launch_quant_p(uint32_t P, uint32_t U, bool nts, dim3 grid, hipStream_t st, const QuantArgs& a) {
-    switch (P) {
-        case 64:   launch_quant_u<64, ALIGNED, GLOBAL, BE, RNE>(U, nts, grid, st, a); break;
-        case 128:  launch_quant_u<128, ALIGNED, GLOBAL, BE, RNE>(U, nts, grid, st, a); break;
-        case 256:  launch_quant_u<256, ALIGNED, GLOBAL, BE, RNE>(U, nts, grid, st, a); break;
-        case 512:  launch_quant_u<512, ALIGNED, GLOBAL, BE, RNE>(U, nts, grid, st, a); break;
-        default:   launch_quant_u<1024, ALIGNED, GLOBAL, BE, RNE>(U, nts, grid, st, a); break;
-    }
-}
-
 // Slices per K1/K2/K3 tile: 4 (1024-element tiles), 2 or 1 (never below
 // P / 256), or 0 = the default, 2 for every kernel (sml_set_quantize_tile_slices).
 // Final kernels (early loads, sc1 nt stores; profiles/r04/ab_slices_final.json,
@@ -491,103 +458,6 @@ static uint32_t quant_slices(uint32_t P) {
     uint32_t want = g_quant_slices.load(std::memory_order_relaxed);
     if (want == 0) want = 2u;
     return want > need ? want : need;
-}
-
-template <bool ALIGNED, bool GLOBAL, bool BE>
-static void launch_quant_r(bool rne, uint32_t P, uint32_t U, bool nts, dim3 g, hipStream_t st, const QuantArgs& a) {
-    if (rne) launch_quant_p<ALIGNED, GLOBAL, BE, true>(P, U, nts, g, st, a);
-    else launch_quant_p<ALIGNED, GLOBAL, BE, false>(P, U, nts, g, st, a);
-}
-
-template <bool ALIGNED, bool GLOBAL>
-static void launch_quant_b(bool be, bool rne, uint32_t P, uint32_t U, bool nts, dim3 g, hipStream_t st,
-                           const QuantArgs& a) {
-    if (be) launch_quant_r<ALIGNED, GLOBAL, true>(rne, P, U, nts, g, st, a);
-    else launch_quant_r<ALIGNED, GLOBAL, false>(rne, P, U, nts, g, st, a);
-}
-
-template <bool ALIGNED, bool BE, bool RCP, bool NT, int U>
-static void launch_deq_pn(uint32_t P, dim3 grid, hipStream_t st, const DequantArgs& a) {
-    switch (P) {
-        case 64:   k_dequantize<64, ALIGNED, BE, RCP, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 128:  k_dequantize<128, ALIGNED, BE, RCP, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 256:  k_dequantize<256, ALIGNED, BE, RCP, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 512:  k_dequantize<512, ALIGNED, BE, RCP, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        default:   k_dequantize<1024, ALIGNED, BE, RCP, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-    }
-}
-
-template <bool ALIGNED, bool BE, bool RCP>
-static void launch_deq_p(uint32_t P, uint32_t U, bool nt, dim3 grid, hipStream_t st, const DequantArgs& a) {
-    if (U == 2) {
-        if (nt) launch_deq_pn<ALIGNED, BE, RCP, true, 2>(P, grid, st, a);
-        else launch_deq_pn<ALIGNED, BE, RCP, false, 2>(P, grid, st, a);
-        return;
-    }
-    if (nt) launch_deq_pn<ALIGNED, BE, RCP, true, 4>(P, grid, st, a);
-    else launch_deq_pn<ALIGNED, BE, RCP, false, 4>(P, grid, st, a);
-}
-
-template <bool ALIGNED, bool BE>
-static void launch_deq_w(uint32_t P, uint32_t U, bool nt, dim3 grid, hipStream_t st, const DequantArgs& a) {
-    if ((a.W & (a.W - 1)) == 0) launch_deq_p<ALIGNED, BE, true>(P, U, nt, grid, st, a);
-    else launch_deq_p<ALIGNED, BE, false>(P, U, nt, grid, st, a);
-}
-
-template <bool ALIGNED, bool BE, bool RNE, bool NT, int U>
-static void launch_rt_pn(uint32_t P, dim3 grid, hipStream_t st, const RoundTripArgs& a) {
-    switch (P) {
-        case 64:   k_roundtrip<64, ALIGNED, BE, RNE, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 128:  k_roundtrip<128, ALIGNED, BE, RNE, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 256:  k_roundtrip<256, ALIGNED, BE, RNE, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 512:  k_roundtrip<512, ALIGNED, BE, RNE, NT, U><<<grid, kBlockThreads, 0, st>>>(a); break;
-        default:   k_roundtrip<1024, ALIGNED, BE, RNE, NT, 4><<<grid, kBlockThreads, 0, st>>>(a); break;   // a tile holds the packet
-    }
-}
-
-template <bool ALIGNED, bool BE, bool RNE>
-static void launch_rt_p(uint32_t P, uint32_t U, bool nt, dim3 grid, hipStream_t st, const RoundTripArgs& a) {
-    if (U == 2) {
-        if (nt) launch_rt_pn<ALIGNED, BE, RNE, true, 2>(P, grid, st, a);
-        else launch_rt_pn<ALIGNED, BE, RNE, false, 2>(P, grid, st, a);
-        return;
-    }
-    if (nt) launch_rt_pn<ALIGNED, BE, RNE, true, 4>(P, grid, st, a);
-    else launch_rt_pn<ALIGNED, BE, RNE, false, 4>(P, grid, st, a);
-}
-
-template <bool RNE, bool NT>
-static void launch_rtb_pn(uint32_t P, uint32_t U, dim3 grid, hipStream_t st, const RoundTripBatchArgs& a) {
-    // a tile holds whole packets: P = 1024 runs 4 slices
-    if (U == 2) {
-        switch (P) {
-            case 64:   k_roundtrip_batch<64, RNE, NT, 2><<<grid, kBlockThreads, 0, st>>>(a); return;
-            case 128:  k_roundtrip_batch<128, RNE, NT, 2><<<grid, kBlockThreads, 0, st>>>(a); return;
-            case 256:  k_roundtrip_batch<256, RNE, NT, 2><<<grid, kBlockThreads, 0, st>>>(a); return;
-            case 512:  k_roundtrip_batch<512, RNE, NT, 2><<<grid, kBlockThreads, 0, st>>>(a); return;
-            default:   break;
-        }
-    }
-    switch (P) {
-        case 64:   k_roundtrip_batch<64, RNE, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 128:  k_roundtrip_batch<128, RNE, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 256:  k_roundtrip_batch<256, RNE, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 512:  k_roundtrip_batch<512, RNE, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-        default:   k_roundtrip_batch<1024, RNE, NT><<<grid, kBlockThreads, 0, st>>>(a); break;
-    }
-}
-
-template <bool RNE>
-static void launch_rtb_p(uint32_t P, uint32_t U, bool nt, dim3 grid, hipStream_t st, const RoundTripBatchArgs& a) {
-    if (nt) launch_rtb_pn<RNE, true>(P, U, grid, st, a);
-    else launch_rtb_pn<RNE, false>(P, U, grid, st, a);
-}
-
-template <bool ALIGNED>
-static void launch_rt_a(bool be, bool rne, bool nt, uint32_t P, uint32_t U, dim3 g, hipStream_t st,
-                        const RoundTripArgs& a) {
-    if (be) { if (rne) launch_rt_p<ALIGNED, true, true>(P, U, nt, g, st, a); else launch_rt_p<ALIGNED, true, false>(P, U, nt, g, st, a); }
-    else    { if (rne) launch_rt_p<ALIGNED, false, true>(P, U, nt, g, st, a); else launch_rt_p<ALIGNED, false, false>(P, U, nt, g, st, a); }
 }
 
 }  // namespace sml
@@ -660,8 +530,7 @@ static sml_status_t quantize_common(const float* d_in, uint64_t numel, uint32_t 
     if (d_payload && !aligned16(d_payload)) return SML_ERR_ALIGNMENT;
     QuantArgs a;
     const uint32_t U = quant_slices(P);
-    // XCD runs keep their byte length (C workgroups of 4 U-slice tiles)
-    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed) * (4 / U);
+    a.xcd = xcd_chunk_for(U);
     a.in = d_in;
     a.numel = numel;
     a.nblocks = sml_num_blocks(numel, P);
@@ -675,14 +544,23 @@ static sml_status_t quantize_common(const float* d_in, uint64_t numel, uint32_t 
     hipStream_t st = (hipStream_t)stream;
     const bool al = aligned16(d_in), be = !(flags & SML_FLAG_PAYLOAD_LE), rne = flags & SML_FLAG_ROUND_RNE;
     // payload store policy by plane size
-    const bool nts = d_payload && 4 * numel >= g_nt_threshold.load(std::memory_order_relaxed);
-    if (d_gexp) {
-        if (al) launch_quant_b<true, true>(be, rne, P, U, nts, grid, st, a);
-        else launch_quant_b<false, true>(be, rne, P, U, nts, grid, st, a);
-    } else {
-        if (al) launch_quant_b<true, false>(be, rne, P, U, nts, grid, st, a);
-        else launch_quant_b<false, false>(be, rne, P, U, nts, grid, st, a);
-    }
+    const bool nts = d_payload && nt_from(4 * numel);
+    // Flags outermost, the store policy innermost: the order in which the
+    // instances are created.  hipcc's code for twelve K3 instances (P = 128 /
+    // 256, one slice) differs with it — registers and block layout, same
+    // arithmetic — and this order gives the code that was measured.
+    dispatch_bools([&](auto GLOBAL, auto AL, auto BE, auto RNE) {
+        dispatch_packet(P, [&](auto Pc) {
+            dispatch_slices<1, 2, 4>(U, [&](auto Uc) {
+                dispatch_bools([&](auto NTS) {
+                    // a tile holds whole packets: fewer than P / 256 slices cannot
+                    // occur (quant_slices) and would run 4
+                    constexpr int kUc = Uc() * 256 >= Pc() ? Uc() : 4;
+                    k_quantize_pack<Pc(), AL(), GLOBAL(), BE(), RNE(), kUc, NTS()><<<grid, kBlockThreads, 0, st>>>(a);
+                }, nts);
+            });
+        });
+    }, d_gexp != nullptr, al, be, rne);
     return launch_check();
 }
 
@@ -713,7 +591,7 @@ sml_status_t sml_dequantize(const int32_t* d_payload, const int8_t* d_exps, uint
     if (!aligned16(d_payload)) return SML_ERR_ALIGNMENT;
     DequantArgs a;
     const uint32_t U = stream_slices(2);   // measured: 2-slice tiles +0.6 / +2.8 / +3.3 % at 128 / 256 / 512 MiB
-    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed) * (4 / U);   // XCD runs keep their byte length
+    a.xcd = xcd_chunk_for(U);
     a.payload = reinterpret_cast<const u4*>(d_payload);
     a.exps = d_exps;
     a.out = d_out;
@@ -723,9 +601,15 @@ sml_status_t sml_dequantize(const int32_t* d_payload, const int8_t* d_exps, uint
     dim3 grid(grid_for_tiles(a.ntiles));
     hipStream_t st = (hipStream_t)stream;
     const bool al = aligned16(d_out), be = !(flags & SML_FLAG_PAYLOAD_LE);
-    const bool nt = 4 * numel >= g_nt_threshold.load(std::memory_order_relaxed);   // output plane past the Infinity Cache
-    if (al) { if (be) launch_deq_w<true, true>(packet_numel, U, nt, grid, st, a); else launch_deq_w<true, false>(packet_numel, U, nt, grid, st, a); }
-    else    { if (be) launch_deq_w<false, true>(packet_numel, U, nt, grid, st, a); else launch_deq_w<false, false>(packet_numel, U, nt, grid, st, a); }
+    const bool rcp = (a.W & (a.W - 1)) == 0;   // power-of-two W: exact reciprocal
+    const bool nt = nt_from(4 * numel);        // output plane past the Infinity Cache
+    dispatch_packet(packet_numel, [&](auto Pc) {
+        dispatch_slices<2, 4>(U, [&](auto Uc) {
+            dispatch_bools([&](auto AL, auto BE, auto RCP, auto NT) {
+                k_dequantize<Pc(), AL(), BE(), RCP(), NT(), Uc()><<<grid, kBlockThreads, 0, st>>>(a);
+            }, al, be, rcp, nt);
+        });
+    });
     return launch_check();
 }
 
@@ -741,7 +625,7 @@ sml_status_t sml_roundtrip_loopback(const float* d_in, float* d_out, uint64_t nu
     RoundTripArgs a;
     // a tile holds whole packets: P = 1024 needs 4 slices
     const uint32_t U = packet_numel > 512 ? 4u : stream_slices(2);
-    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed) * (4 / U);
+    a.xcd = xcd_chunk_for(U);
     a.in = d_in;
     a.out = d_out;
     a.numel = numel;
@@ -756,9 +640,16 @@ sml_status_t sml_roundtrip_loopback(const float* d_in, float* d_out, uint64_t nu
     // unless the caller passed differently aligned buffers.
     const bool al = aligned16(d_in) && aligned16(d_out);
     const bool be = !(flags & SML_FLAG_PAYLOAD_LE), rne = flags & SML_FLAG_ROUND_RNE;
-    const bool nt = 4 * numel >= g_nt_threshold.load(std::memory_order_relaxed);   // output plane past the Infinity Cache
-    if (al) launch_rt_a<true>(be, rne, nt, packet_numel, U, grid, st, a);
-    else launch_rt_a<false>(be, rne, nt, packet_numel, U, grid, st, a);
+    const bool nt = nt_from(4 * numel);   // output plane past the Infinity Cache
+    dispatch_packet(packet_numel, [&](auto Pc) {
+        dispatch_slices<2, 4>(U, [&](auto Uc) {
+            dispatch_bools([&](auto AL, auto BE, auto RNE, auto NT) {
+                // P = 1024 always runs 4 slices (U above): a tile holds the packet
+                constexpr int kUc = Pc() == 1024 ? 4 : Uc();
+                k_roundtrip<Pc(), AL(), BE(), RNE(), NT(), kUc><<<grid, kBlockThreads, 0, st>>>(a);
+            }, al, be, rne, nt);
+        });
+    });
     return launch_check();
 }
 
@@ -772,7 +663,7 @@ sml_status_t sml_roundtrip_loopback_batch(const sml_slice* slices, uint32_t num_
     // 25 MiB buckets 36.10 -> 35.32 us (profiles/r04/ab_batch_slices.json).
     const uint32_t U = packet_numel > 512 ? 4u : 2u;
     const uint64_t tile = (uint64_t)U * kWave * 4;
-    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed) * (4 / U);   // XCD runs keep their byte length
+    a.xcd = xcd_chunk_for(U);
     a.W = num_workers;
     a.nslices = 0;
     uint64_t tiles = 0;
@@ -797,9 +688,16 @@ sml_status_t sml_roundtrip_loopback_batch(const sml_slice* slices, uint32_t num_
     // the outputs of the whole batch past the Infinity Cache: non-temporal stores
     uint64_t out_bytes = 0;
     for (uint32_t i = 0; i < a.nslices; i++) out_bytes += 4 * a.numel[i];
-    const bool nt = out_bytes >= g_nt_threshold.load(std::memory_order_relaxed);
-    if (flags & SML_FLAG_ROUND_RNE) launch_rtb_p<true>(packet_numel, U, nt, grid, st, a);
-    else launch_rtb_p<false>(packet_numel, U, nt, grid, st, a);
+    const bool rne = flags & SML_FLAG_ROUND_RNE, nt = nt_from(out_bytes);
+    dispatch_packet(packet_numel, [&](auto Pc) {
+        dispatch_slices<2, kU>(U, [&](auto Uc) {
+            dispatch_bools([&](auto RNE, auto NT) {
+                // P = 1024 always runs the default slices (U above): a tile holds the packet
+                constexpr int kUc = Pc() <= 512 ? Uc() : kU;
+                k_roundtrip_batch<Pc(), RNE(), NT(), kUc><<<grid, kBlockThreads, 0, st>>>(a);
+            }, rne, nt);
+        });
+    });
     return launch_check();
 }
 
@@ -840,17 +738,17 @@ sml_status_t sml_stream_copy(const void* d_in, void* d_out, uint64_t bytes, void
     // output plane of `bytes` (sml_quantize_pack)
     const uint32_t U = quant_slices(256);
     const uint64_t ntiles = bytes / (256 * U * 4);
-    const uint32_t xcd = g_xcd_chunk.load(std::memory_order_relaxed) * (4 / U);
+    const uint32_t xcd = xcd_chunk_for(U);
     auto in = reinterpret_cast<const u4*>(d_in);
     auto out = reinterpret_cast<u4*>(d_out);
-    const bool nts = bytes >= g_nt_threshold.load(std::memory_order_relaxed);
+    const bool nts = nt_from(bytes);
     const dim3 grid(grid_for_tiles(ntiles));
     hipStream_t st = (hipStream_t)stream;
-#define SML_COPY(U_)                                                                     \
-    if (nts) k_stream_copy<true, U_><<<grid, kBlockThreads, 0, st>>>(in, out, ntiles, xcd); \
-    else k_stream_copy<false, U_><<<grid, kBlockThreads, 0, st>>>(in, out, ntiles, xcd);
-    if (U == 1) { SML_COPY(1) } else if (U == 2) { SML_COPY(2) } else { SML_COPY(4) }
-#undef SML_COPY
+    dispatch_slices<1, 2, 4>(U, [&](auto Uc) {
+        dispatch_bools([&](auto NTS) {
+            k_stream_copy<NTS(), Uc()><<<grid, kBlockThreads, 0, st>>>(in, out, ntiles, xcd);
+        }, nts);
+    });
     return launch_check();
 }
 

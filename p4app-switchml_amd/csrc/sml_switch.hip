@@ -247,24 +247,6 @@ __global__ __launch_bounds__(kBlockThreads) void k_copy_segments(SegCopyArgs a) 
     }
 }
 
-template <bool ALIGNED, bool BE, bool RCP, bool EXPS>
-static void launch_switch_p(uint32_t P, dim3 grid, hipStream_t st, const SwitchArgs& a) {
-    switch (P) {
-        case 64:   k_switch_aggregate<64, ALIGNED, BE, RCP, EXPS><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 128:  k_switch_aggregate<128, ALIGNED, BE, RCP, EXPS><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 256:  k_switch_aggregate<256, ALIGNED, BE, RCP, EXPS><<<grid, kBlockThreads, 0, st>>>(a); break;
-        case 512:  k_switch_aggregate<512, ALIGNED, BE, RCP, EXPS><<<grid, kBlockThreads, 0, st>>>(a); break;
-        default:   k_switch_aggregate<1024, ALIGNED, BE, RCP, EXPS><<<grid, kBlockThreads, 0, st>>>(a); break;
-    }
-}
-
-template <bool ALIGNED, bool BE>
-static void launch_switch_m(bool exps, bool rcp, uint32_t P, dim3 g, hipStream_t st, const SwitchArgs& a) {
-    if (!exps) launch_switch_p<ALIGNED, BE, false, false>(P, g, st, a);
-    else if (rcp) launch_switch_p<ALIGNED, BE, true, true>(P, g, st, a);
-    else launch_switch_p<ALIGNED, BE, false, true>(P, g, st, a);
-}
-
 // ncclUint8 buckets (the CollNet plugin, switchml_plugin.cc:318-337 and
 // 370-378): widened to int32 for the INT32 all-reduce, narrowed back (mod 256).
 __global__ __launch_bounds__(kBlockThreads) void k_widen_u8(const uint8_t* in, int32_t* out, uint64_t n) {
@@ -321,11 +303,15 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
     const dim3 grid(grid_for_tiles(a.ntiles));
     const hipStream_t st = (hipStream_t)stream;
     const bool al = !d_out || aligned16(d_out), be = !(flags & SML_FLAG_PAYLOAD_LE);
-    const bool rcp = (num_workers & (num_workers - 1)) == 0;
-    if (al) { if (be) launch_switch_m<true, true>(exps, rcp, packet_numel, grid, st, a);
-              else launch_switch_m<true, false>(exps, rcp, packet_numel, grid, st, a); }
-    else    { if (be) launch_switch_m<false, true>(exps, rcp, packet_numel, grid, st, a);
-              else launch_switch_m<false, false>(exps, rcp, packet_numel, grid, st, a); }
+    // the reciprocal form is the fp32 output's, which needs the exponents
+    const bool rcp = exps && (num_workers & (num_workers - 1)) == 0;
+    dispatch_packet(packet_numel, [&](auto Pc) {
+        dispatch_bools([&](auto AL, auto BE, auto RCP, auto EXPS) {
+            // RCP without EXPS cannot occur (rcp above): not instantiated
+            if constexpr (EXPS() || !RCP())
+                k_switch_aggregate<Pc(), AL(), BE(), RCP(), EXPS()><<<grid, kBlockThreads, 0, st>>>(a);
+        }, al, be, rcp, exps);
+    });
     return launch_check();
 }
 
