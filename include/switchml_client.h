@@ -30,7 +30,8 @@ extern "C" {
 enum { SML_CTX_CREATED = 0, SML_CTX_STARTING, SML_CTX_RUNNING, SML_CTX_STOPPING, SML_CTX_STOPPED };
 enum { SML_JOB_INIT = 0, SML_JOB_QUEUED, SML_JOB_RUNNING, SML_JOB_FINISHED, SML_JOB_FAILED };
 /* DataType (common.h:51-55) and AllReduceOperation (job.h:44-46) */
-enum { SML_DT_FLOAT32 = 0, SML_DT_INT32 = 1 };
+/* FLOAT16 / BFLOAT16 jobs are converted inside the kernels (bulk and fused modes of the dummy backend) */
+enum { SML_DT_FLOAT32 = 0, SML_DT_INT32 = 1, SML_DT_FLOAT16 = 2, SML_DT_BFLOAT16 = 3 };
 enum { SML_OP_SUM = 0 };
 
 typedef struct sml_job_s* sml_job_t;

@@ -52,7 +52,12 @@ typedef enum {
 } sml_status_t;
 
 /* client_lib/src/common.h:51-55 */
-typedef enum { SML_FLOAT32 = 0, SML_INT32 = 1 } sml_data_type_t;
+typedef enum {
+    SML_FLOAT32 = 0,
+    SML_INT32 = 1,
+    SML_FLOAT16 = 2,    /* IEEE binary16; the sml_*_typed entry points only */
+    SML_BFLOAT16 = 3    /* bfloat16; the sml_*_typed entry points only */
+} sml_data_type_t;
 
 /* flags for the quantize / dequantize entry points */
 #define SML_FLAG_PAYLOAD_LE   0x1u  /* payload plane in host (little-endian) order: the
@@ -177,6 +182,43 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
                                   uint16_t num_workers, uint64_t numel, uint32_t packet_numel,
                                   int32_t* d_payload_out, int8_t* d_exps_out, float* d_out,
                                   uint32_t flags, void* stream);
+
+/* ---- FLOAT16 / BFLOAT16 job slices ----------------------------------------
+ * The typed counterparts of sml_exponents, sml_quantize_pack, sml_dequantize,
+ * sml_roundtrip_loopback and sml_switch_aggregate: the same argument lists,
+ * with void* for the typed buffer and its sml_data_type_t next to it.
+ *   SML_FLOAT16 / SML_BFLOAT16: the kernels convert.  x32[i] = (float)x[i]
+ *     (exact) right after the load; everything between is the FLOAT32 path on
+ *     x32, unchanged (block exponent, scale, roundf or SML_FLAG_ROUND_RNE, the
+ *     big-endian pack, the dequantize to an fp32 y32); y[i] = (T)y32[i], round
+ *     to nearest even, right before the store (overflow -> +-inf, fp16 results
+ *     below the normal range -> fp16 denormals, NaN -> a NaN of T).  The planes
+ *     are the FLOAT32 ones: int32 payload words and one int8 exponent per
+ *     packet of P elements, B = ceil(numel / P) whatever the element size.
+ *   SML_FLOAT32: forwards to the untyped entry point (same kernels, same bits).
+ *   SML_INT32 (or any other value): SML_ERR_UNSUPPORTED.
+ * Typed buffers of a 16-bit type need 2-byte alignment only (a slice starts
+ * at any element) and no byte outside [ptr, ptr + 2 * numel) is touched;
+ * payload planes 16-byte aligned, as above.  in == out is allowed for the
+ * round trip.  The burst, frames, RDMA and batch entry points take no 16-bit
+ * type (a burst whose data_type is one returns SML_ERR_UNSUPPORTED). */
+sml_status_t sml_exponents_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
+                                 uint32_t packet_numel, int8_t* d_exps, void* stream);
+sml_status_t sml_quantize_pack_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
+                                     uint32_t packet_numel, uint16_t num_workers,
+                                     const int8_t* d_global_exps, int32_t* d_payload, int8_t* d_exps_out,
+                                     uint32_t flags, void* stream);
+sml_status_t sml_dequantize_typed(const int32_t* d_payload, const int8_t* d_exps, uint64_t numel,
+                                  uint32_t packet_numel, uint16_t num_workers, void* d_out,
+                                  sml_data_type_t data_type, uint32_t flags, void* stream);
+sml_status_t sml_roundtrip_loopback_typed(const void* d_in, void* d_out, sml_data_type_t data_type,
+                                          uint64_t numel, uint32_t packet_numel, uint16_t num_workers,
+                                          int32_t* d_payload, int8_t* d_exps_out,
+                                          uint32_t flags, void* stream);
+sml_status_t sml_switch_aggregate_typed(const int32_t* const* d_payloads, const int8_t* const* d_exps,
+                                        uint16_t num_workers, uint64_t numel, uint32_t packet_numel,
+                                        int32_t* d_payload_out, int8_t* d_exps_out, void* d_out,
+                                        sml_data_type_t data_type, uint32_t flags, void* stream);
 
 /* The switch's exponent half alone (p4/exponents.p4:48-54): d_exps_out[k] =
  * max_w (int8) d_exps[w][k], k < num_blocks — W planes of num_blocks bytes

@@ -60,7 +60,7 @@ const char* sml_context_config(void) {
 }
 
 int sml_allreduce_async(void* in_ptr, void* out_ptr, uint64_t numel, int data_type, int op, sml_job_t* job) {
-    if (!job || (data_type != SML_DT_FLOAT32 && data_type != SML_DT_INT32) || op != SML_OP_SUM)
+    if (!job || data_type < SML_DT_FLOAT32 || data_type > SML_DT_BFLOAT16 || op != SML_OP_SUM)
         return fail(SML_CTX_ERR_ARG, "invalid argument");
     if (numel && (!in_ptr || !out_ptr)) return fail(SML_CTX_ERR_ARG, "null tensor pointer");
     try {

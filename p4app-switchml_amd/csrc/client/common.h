@@ -20,8 +20,23 @@ typedef int16_t WorkerTid;
 typedef uint64_t Numel;
 typedef std::chrono::steady_clock clock;
 
-// common.h:51-55
-enum DataType { FLOAT32, INT32 };
+// common.h:51-55; FLOAT16 (IEEE binary16) and BFLOAT16 are this build's: the
+// kernels widen them to fp32 on the way in and narrow on the way out, so they
+// travel as FLOAT32 does (int32 words, one exponent per packet).
+enum DataType { FLOAT32, INT32, FLOAT16, BFLOAT16 };
+
+inline bool IsHalfType(DataType type) { return type == FLOAT16 || type == BFLOAT16; }
+// Float types are quantized: an exponent per packet, hence the extra batch.
+inline bool IsFloatType(DataType type) { return type == FLOAT32 || IsHalfType(type); }
+inline const char* DataTypeName(DataType type) {
+    switch (type) {
+        case FLOAT32: return "FLOAT32";
+        case INT32: return "INT32";
+        case FLOAT16: return "FLOAT16";
+        case BFLOAT16: return "BFLOAT16";
+    }
+    return "?";
+}
 
 // job.h:36-39 / 44-46
 enum JobType { ALLREDUCE, BROADCAST };
@@ -41,6 +56,7 @@ class SwitchMLFatal : public std::runtime_error {
 // common.h:62-70
 inline uint16_t DataTypeSize(DataType type) {
     if (type == FLOAT32 || type == INT32) return 4;
+    if (type == FLOAT16 || type == BFLOAT16) return 2;
     throw SwitchMLFatal("'" + std::to_string((int)type) + "' is not a valid tensor data type");
 }
 
@@ -58,6 +74,14 @@ struct Tensor {
         out_ptr = static_cast<char*>(out_ptr) + bytes;
     }
 };
+
+// Bytes a slice takes on the wire: every element travels as one 32-bit word,
+// a 16-bit element too (a packet is ltu_size / 4 words whatever the type), so
+// the packet count is ceil(numel / P) and never halves for 2-byte elements.
+inline Numel WireBytes(const Tensor& t) {
+    (void)DataTypeSize(t.data_type);   // throws on an invalid type
+    return t.numel * 4;
+}
 
 // How long a waiter polls before it sleeps (job completion, a worker's
 // stream, an idle worker waiting for the next job), in microseconds.

@@ -116,6 +116,14 @@ class Config {
     // config.cc:154-213 (general part): mop must give every worker thread a
     // packet; mop is rounded to a multiple of num_worker_threads.
     void Validate();
+    // Whether this configuration runs FLOAT16 / BFLOAT16 jobs: the dummy
+    // backend's bulk and fused modes convert them inside the kernels (and the
+    // bypass PPP moves no data, whatever the mode); mode = packet and
+    // backend = xgmi refuse such a job, which then ends FAILED.
+    bool RunsHalfTypes() const {
+        return general_.backend == "dummy" && (general_.prepostprocessor == "bypass" ||
+                                               backend_.hip.mode == "bulk" || backend_.hip.mode == "fused");
+    }
     std::string ToString() const;
     void PrintConfig() const;
 };

@@ -64,13 +64,24 @@ uint64_t HipExponentQuantizerPPP::SetupJobSlice(JobSlice* job_slice) {
     pool_probe_ = nullptr;
     xpool_probe_ = nullptr;
     dev_of_.clear();
-    const uint64_t bytes = job_slice->slice.numel * DataTypeSize(job_slice->slice.data_type);
+    const uint64_t bytes = WireBytes(job_slice->slice);   // words, not elements' bytes: B = ceil(numel / P)
     total_main_num_ltus_ = (bytes + ltu_size_ - 1) / ltu_size_;
     batch_num_ltus_ = std::min<uint64_t>(total_main_num_ltus_, batch_max_num_ltus_);
     return total_main_num_ltus_;
 }
 
-bool HipExponentQuantizerPPP::NeedsExtraBatch() { return job_slice_->slice.data_type == FLOAT32; }
+bool HipExponentQuantizerPPP::NeedsExtraBatch() { return IsFloatType(job_slice_->slice.data_type); }
+
+// FLOAT16 / BFLOAT16 slices run through the bulk hooks and the fused round
+// trip only; every per-packet path refuses them by name rather than run them
+// as another type.
+void HipExponentQuantizerPPP::refuse_half(const char* call) const {
+    const DataType dt = job_slice_->slice.data_type;
+    if (IsHalfType(dt))
+        throw SwitchMLFatal(std::string(call) + ": " + DataTypeName(dt) +
+                            " jobs are not supported by the per-LTU and burst hooks (backend.hip.mode = packet); "
+                            "set backend.hip.mode = bulk or fused");
+}
 
 void HipExponentQuantizerPPP::CleanupJobSlice() {
     job_slice_ = nullptr;
@@ -136,6 +147,7 @@ void HipExponentQuantizerPPP::PostprocessSingle(uint64_t ltu_id, void* entries_p
 }
 
 void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info) {
+    refuse_half("PreprocessSingle");
     const Tensor& s = job_slice_->slice;
     const uint32_t P = (uint32_t)ltu_numel_;
     ensure_single_buffers();
@@ -185,6 +197,7 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
 // words, ltu_size bytes); the caller may reuse a host-memory packet buffer
 // as soon as this returns, so those calls synchronise.
 void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info) {
+    refuse_half("PostprocessSingle");
     const Tensor& s = job_slice_->slice;
     const uint32_t P = (uint32_t)ltu_numel_;
     ensure_single_buffers();
@@ -237,6 +250,10 @@ void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_
 void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* ltu_ids, void* const* entries,
                                    void* const* extras) {
     if (n == 0) return;
+    refuse_half(kind == BurstKind::kPre        ? "PreprocessBurst"
+                : kind == BurstKind::kPost     ? "PostprocessBurst"
+                : kind == BurstKind::kExchange ? "PostprocessReuseBurst"
+                                               : "ProcessPostprocessReuseBurst");
     const Tensor& s = job_slice_->slice;
     const bool flt = s.data_type == FLOAT32;
     const uint64_t total = total_main_num_ltus_ + (flt ? batch_num_ltus_ : 0);
@@ -345,6 +362,7 @@ void HipExponentQuantizerPPP::PostprocessBurst(uint32_t n, const uint64_t* ltu_i
 
 void HipExponentQuantizerPPP::PostprocessReuseBurst(uint32_t n, const uint64_t* ltu_ids, void* const* entries,
                                                     void* const* extras, uint64_t batch, uint64_t total_ltus) {
+    refuse_half("PostprocessReuseBurst");
     const bool flt = job_slice_->slice.data_type == FLOAT32;
     if (batch != batch_num_ltus_ || total_ltus != total_main_num_ltus_ + (flt ? batch_num_ltus_ : 0))
         throw SwitchMLFatal("PostprocessReuseBurst: batch / total_ltus differ from the slice's b / B (+ b)");
@@ -358,21 +376,21 @@ void HipExponentQuantizerPPP::ProcessPostprocessReuseBurst(uint32_t n, const uin
 
 void HipExponentQuantizerPPP::ExponentsBulk(void* exps_plane) {
     const Tensor& s = job_slice_->slice;
-    if (s.data_type != FLOAT32) return;
-    check(sml_exponents(static_cast<const float*>(s.in_ptr), s.numel, (uint32_t)ltu_numel_,
-                        static_cast<int8_t*>(exps_plane), stream_),
+    if (!IsFloatType(s.data_type)) return;
+    check(sml_exponents_typed(s.in_ptr, SmlFloatType(s.data_type), s.numel, (uint32_t)ltu_numel_,
+                              static_cast<int8_t*>(exps_plane), stream_),
           "sml_exponents");
 }
 
 void HipExponentQuantizerPPP::PreprocessBulk(void* payload_plane, void* exps_plane, const void* global_exps,
                                              bool payload_le) {
     const Tensor& s = job_slice_->slice;
-    if (s.data_type == FLOAT32) {
-        check(sml_quantize_pack(static_cast<const float*>(s.in_ptr), s.numel, (uint32_t)ltu_numel_,
-                                config_.general_.num_workers, static_cast<const int8_t*>(global_exps),
-                                static_cast<int32_t*>(payload_plane),
-                                global_exps ? nullptr : static_cast<int8_t*>(exps_plane),
-                                (payload_le ? SML_FLAG_PAYLOAD_LE : 0u) | round_flags_, stream_),
+    if (IsFloatType(s.data_type)) {   // FLOAT32 forwards to sml_quantize_pack
+        check(sml_quantize_pack_typed(s.in_ptr, SmlFloatType(s.data_type), s.numel, (uint32_t)ltu_numel_,
+                                      config_.general_.num_workers, static_cast<const int8_t*>(global_exps),
+                                      static_cast<int32_t*>(payload_plane),
+                                      global_exps ? nullptr : static_cast<int8_t*>(exps_plane),
+                                      (payload_le ? SML_FLAG_PAYLOAD_LE : 0u) | round_flags_, stream_),
               "sml_quantize_pack");
     } else {
         if (payload_le)
@@ -387,10 +405,10 @@ void HipExponentQuantizerPPP::PreprocessBulk(void* payload_plane, void* exps_pla
 
 void HipExponentQuantizerPPP::PostprocessBulk(const void* payload_plane, const void* global_exps, bool payload_le) {
     const Tensor& s = job_slice_->slice;
-    if (s.data_type == FLOAT32) {
-        check(sml_dequantize(static_cast<const int32_t*>(payload_plane), static_cast<const int8_t*>(global_exps),
-                             s.numel, (uint32_t)ltu_numel_, config_.general_.num_workers,
-                             static_cast<float*>(s.out_ptr), payload_le ? SML_FLAG_PAYLOAD_LE : 0u, stream_),
+    if (IsFloatType(s.data_type)) {   // FLOAT32 forwards to sml_dequantize
+        check(sml_dequantize_typed(static_cast<const int32_t*>(payload_plane), static_cast<const int8_t*>(global_exps),
+                                   s.numel, (uint32_t)ltu_numel_, config_.general_.num_workers, s.out_ptr,
+                                   SmlFloatType(s.data_type), payload_le ? SML_FLAG_PAYLOAD_LE : 0u, stream_),
               "sml_dequantize");
     } else {
         if (payload_le)

@@ -24,6 +24,11 @@
 
 namespace switchml {
 
+// The C-ABI's name of a float DataType, for the sml_*_typed entry points.
+inline sml_data_type_t SmlFloatType(DataType dt) {
+    return dt == FLOAT16 ? SML_FLOAT16 : dt == BFLOAT16 ? SML_BFLOAT16 : SML_FLOAT32;
+}
+
 class HipExponentQuantizerPPP : public PrePostProcessor {
   public:
     // per_ltu_calls = false: PreprocessSingle / PostprocessSingle called from
@@ -77,6 +82,7 @@ class HipExponentQuantizerPPP : public PrePostProcessor {
   private:
     void check(int status, const char* what) const;
     void refuse_per_ltu(const char* call) const;
+    void refuse_half(const char* call) const;   // throws for a FLOAT16 / BFLOAT16 slice
     void preprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);
     void postprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);
     void ensure_single_buffers();

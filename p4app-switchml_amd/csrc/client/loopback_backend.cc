@@ -179,6 +179,11 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
     }
     hipStream_t st = ppp->stream();
     Tensor& t = js.slice;
+    const std::string& mode = cfg.backend_.hip.mode;
+    // FLOAT16 / BFLOAT16: the bulk hooks and the fused round trip convert
+    // inside the kernels; the per-packet loop's first burst hook and the
+    // in-node switch (XgmiSwitch::AllReduceSlice) throw for such a slice,
+    // before anything is written, rather than run it as another type
     const size_t bytes = t.numel * DataTypeSize(t.data_type);
     // Device tensors are used in place; pinned host tensors too, through
     // their device mapping (the kernels read and write them over PCIe, both
@@ -203,8 +208,7 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
     const uint64_t B = ppp->SetupJobSlice(&staged);
     const uint64_t P = ppp->ltu_numel();
     const uint16_t W = cfg.general_.num_workers;
-    const std::string& mode = cfg.backend_.hip.mode;
-    const bool is_float = t.data_type == FLOAT32;
+    const bool is_float = IsFloatType(t.data_type);
     uint64_t packets = B + (ppp->NeedsExtraBatch() ? ppp->batch_num_ltus() : 0);
 
     if (xs) {
@@ -213,9 +217,10 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
     } else if (mode == "packet") {
         run_packet_loop(*ppp, cfg, ws, ppp->NeedsExtraBatch());
     } else if (mode == "fused" && is_float && cfg.backend_.dummy.process_packets) {
-        sml_ok(sml_roundtrip_loopback(static_cast<const float*>(staged.slice.in_ptr),
-                                      static_cast<float*>(staged.slice.out_ptr), t.numel, (uint32_t)P, W, nullptr,
-                                      nullptr, cfg.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u, st),
+        // FLOAT32 forwards to sml_roundtrip_loopback
+        sml_ok(sml_roundtrip_loopback_typed(staged.slice.in_ptr, staged.slice.out_ptr, SmlFloatType(t.data_type),
+                                            t.numel, (uint32_t)P, W, nullptr, nullptr,
+                                            cfg.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u, st),
                "sml_roundtrip_loopback");
     } else {  // bulk
         void* payload = ws.payload.get(B * P * 4, st);

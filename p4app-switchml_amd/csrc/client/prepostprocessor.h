@@ -108,7 +108,7 @@ class BypassPPP : public PrePostProcessor {
   public:
     BypassPPP(Config& c, WorkerTid t, Numel ltu, Numel batch) : PrePostProcessor(c, t, ltu, batch) {}
     uint64_t SetupJobSlice(JobSlice* s) override {
-        const uint64_t bytes = s->slice.numel * DataTypeSize(s->slice.data_type);
+        const uint64_t bytes = WireBytes(s->slice);
         return (bytes + ltu_size_ - 1) / ltu_size_;
     }
     bool NeedsExtraBatch() override { return false; }

@@ -596,6 +596,11 @@ void XgmiSwitch::IntChunk(int tid, const int32_t* in, int32_t* out, uint64_t n, 
 
 void XgmiSwitch::AllReduceSlice(int tid, const void* in, void* out, uint64_t numel, DataType type, hipStream_t st) {
     if (tid < 0 || tid >= T_) throw SwitchMLFatal("xgmi switch: bad worker thread id");
+    // every worker refuses the same job here, before any barrier (the CollNet
+    // plugin never posts one: its reduceSupport is 0 for these types under xgmi)
+    if (IsHalfType(type))
+        throw SwitchMLFatal(std::string("xgmi switch: ") + DataTypeName(type) +
+                            " jobs are not supported with backend = xgmi; use backend = dummy (mode bulk or fused)");
     if (numel == 0) return;
     if (Wedged()) throw SwitchMLFatal("xgmi switch: an earlier slice's device work did not finish");
     if (shm_->poisoned.load(std::memory_order_acquire))

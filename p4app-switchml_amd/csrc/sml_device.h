@@ -212,6 +212,71 @@ __device__ __forceinline__ void store4_guarded(float* p, f4 v, uint64_t idx, uin
     if (idx + 3 < numel) p[3] = v.w;
 }
 
+// ------------------------------------------------ 16-bit float elements
+// FLOAT16 / BFLOAT16 job slices (sml_half.hip): the element is widened to
+// fp32 in registers right after the load and narrowed right before the store,
+// everything between is the fp32 arithmetic above.  H is the sml_data_type_t
+// value: 2 = IEEE binary16, 3 = bfloat16; elements travel as raw uint16_t.
+constexpr int kHalfF16 = 2;
+constexpr int kHalfBF16 = 3;
+
+// Exact for both types (fp16 denormals become fp32 normals, NaN stays NaN):
+// v_cvt_f32_f16, and a 16-bit shift for bf16.
+template <int H>
+__device__ __forceinline__ float widen16(uint16_t h) {
+    static_assert(H == kHalfF16 || H == kHalfBF16, "fp16 or bf16");
+    if constexpr (H == kHalfF16) return (float)__builtin_bit_cast(_Float16, h);
+    else return __uint_as_float((uint32_t)h << 16);
+}
+
+// Round to nearest even; overflow -> +-inf, fp16 results below the normal
+// range -> fp16 denormals (the units are built without denormal flushing),
+// NaN -> a NaN of the type: v_cvt_f16_f32 / v_cvt_pk_bf16_f32.
+template <int H>
+__device__ __forceinline__ uint16_t narrow16(float f) {
+    static_assert(H == kHalfF16 || H == kHalfBF16, "fp16 or bf16");
+    if constexpr (H == kHalfF16) return __builtin_bit_cast(uint16_t, (_Float16)f);
+    else return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+
+// Four 16-bit elements = one 8-byte access per lane.  Slices start at any
+// element (2-byte alignment): the vector type is declared aligned(2), which
+// gfx950's unaligned-access mode still moves as one dwordx2 per lane.
+typedef uint16_t h4a __attribute__((ext_vector_type(4), aligned(2)));
+
+template <int H>
+__device__ __forceinline__ f4 load4h(const uint16_t* p) {
+    const h4a v = __builtin_nontemporal_load(reinterpret_cast<const h4a*>(p));
+    return mkf4(widen16<H>(v.x), widen16<H>(v.y), widen16<H>(v.z), widen16<H>(v.w));
+}
+
+template <int H>
+__device__ __forceinline__ f4 load4h_guarded(const uint16_t* p, uint64_t idx, uint64_t numel) {
+    f4 v;
+    v.x = idx + 0 < numel ? widen16<H>(p[0]) : 0.0f;
+    v.y = idx + 1 < numel ? widen16<H>(p[1]) : 0.0f;
+    v.z = idx + 2 < numel ? widen16<H>(p[2]) : 0.0f;
+    v.w = idx + 3 < numel ? widen16<H>(p[3]) : 0.0f;
+    return v;
+}
+
+// nt_store16_sc1 takes 16-byte values only: the 8-byte non-temporal form is
+// the builtin's.
+template <int H, bool NT>
+__device__ __forceinline__ void store4h(uint16_t* p, f4 v) {
+    const h4a o = h4a{narrow16<H>(v.x), narrow16<H>(v.y), narrow16<H>(v.z), narrow16<H>(v.w)};
+    if constexpr (NT) __builtin_nontemporal_store(o, reinterpret_cast<h4a*>(p));
+    else *reinterpret_cast<h4a*>(p) = o;
+}
+
+template <int H>
+__device__ __forceinline__ void store4h_guarded(uint16_t* p, f4 v, uint64_t idx, uint64_t numel) {
+    if (idx + 0 < numel) p[0] = narrow16<H>(v.x);
+    if (idx + 1 < numel) p[1] = narrow16<H>(v.y);
+    if (idx + 2 < numel) p[2] = narrow16<H>(v.z);
+    if (idx + 3 < numel) p[3] = narrow16<H>(v.w);
+}
+
 // Payload stores keep the default cache policy: measured 9 % faster than
 // non-temporal stores on the 256 MiB bucket (loads stay non-temporal,
 // which is 15 % faster than default-policy loads) — profiles/r01/ab*.json.

@@ -52,7 +52,7 @@ struct SwitchArgs {
     const int8_t* exps[SML_MAX_SWITCH_WORKERS];
     u4* payload_out;        // nullable: aggregated plane (B*P words)
     int8_t* exps_out;       // nullable: max exponents (B bytes)
-    float* out;             // nullable: dequantized bucket (numel floats)
+    void* out;              // nullable: dequantized bucket (numel elements: fp32, or H's 16-bit type)
     uint64_t numel;
     uint64_t nblocks;       // B
     uint64_t ntiles;        // ceil(B*P / 1024)
@@ -64,8 +64,10 @@ struct SwitchArgs {
 
 // W payload loads per lane-slice are issued before the adds (16-B
 // non-temporal, as K4); exponent bytes come one scalar load per slice and
-// plane when the planes are 4-byte aligned.
-template <int P, bool ALIGNED, bool BE, bool RCP, bool EXPS>
+// plane when the planes are 4-byte aligned.  H = 0: the fp32 bucket; H =
+// kHalfF16 / kHalfBF16: the fp32 value narrowed (round to nearest even) into
+// a 16-bit bucket at any 2-byte alignment (sml_switch_aggregate_typed).
+template <int P, bool ALIGNED, bool BE, bool RCP, bool EXPS, int H = 0>
 __global__ __launch_bounds__(kBlockThreads) void k_switch_aggregate(SwitchArgs a) {
     __shared__ float lut[256];
     acquire_peer_planes(a.flags);
@@ -147,8 +149,15 @@ __global__ __launch_bounds__(kBlockThreads) void k_switch_aggregate(SwitchArgs a
                                  (float)(int32_t)q.w * s);
                     else
                         o = mkf4(dequantize1(q.x, s), dequantize1(q.y, s), dequantize1(q.z, s), dequantize1(q.w, s));
-                    if (idx + 4 <= a.numel) store4<ALIGNED>(a.out + idx, o);
-                    else store4_guarded(a.out + idx, o, idx, a.numel);
+                    if constexpr (H == 0) {
+                        float* out = static_cast<float*>(a.out);
+                        if (idx + 4 <= a.numel) store4<ALIGNED>(out + idx, o);
+                        else store4_guarded(out + idx, o, idx, a.numel);
+                    } else {
+                        uint16_t* out = static_cast<uint16_t*>(a.out);
+                        if (idx + 4 <= a.numel) store4h<H, false>(out + idx, o);
+                        else store4h_guarded<H>(out + idx, o, idx, a.numel);
+                    }
                 }
             }
         }
@@ -266,18 +275,20 @@ using namespace sml;
 
 extern "C" {
 
-sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t* const* d_exps,
-                                  uint16_t num_workers, uint64_t numel, uint32_t packet_numel,
-                                  int32_t* d_payload_out, int8_t* d_exps_out, float* d_out,
-                                  uint32_t flags, void* stream) {
+// dt: the type of d_out (SML_FLOAT32, or a 16-bit float type: the typed entry point)
+static sml_status_t switch_aggregate(const int32_t* const* d_payloads, const int8_t* const* d_exps,
+                                     uint16_t num_workers, uint64_t numel, uint32_t packet_numel,
+                                     int32_t* d_payload_out, int8_t* d_exps_out, void* d_out, sml_data_type_t dt,
+                                     uint32_t flags, void* stream) {
     if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
+    const bool half = dt != SML_FLOAT32;
     if (num_workers == 0 || !d_payloads) return SML_ERR_INVALID_ARG;
     if (num_workers > SML_MAX_SWITCH_WORKERS) return SML_ERR_UNSUPPORTED;
     if (numel == 0) return SML_OK;
     if (!d_payload_out && !d_exps_out && !d_out) return SML_ERR_INVALID_ARG;
     const bool exps = d_exps_out || d_out;
     if (exps && !d_exps) return SML_ERR_INVALID_ARG;
-    if (d_out && !aligned4(d_out)) return SML_ERR_INVALID_ARG;
+    if (d_out && ((uintptr_t)d_out & (half ? 1u : 3u))) return SML_ERR_INVALID_ARG;
     if (d_payload_out && !aligned16(d_payload_out)) return SML_ERR_ALIGNMENT;
     SwitchArgs a{};
     a.exps_scalar = 1;
@@ -302,9 +313,20 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
     a.flags = flags & SML_FLAG_PEER_PLANES;
     const dim3 grid(grid_for_tiles(a.ntiles));
     const hipStream_t st = (hipStream_t)stream;
-    const bool al = !d_out || aligned16(d_out), be = !(flags & SML_FLAG_PAYLOAD_LE);
+    // a 16-bit bucket has one store form (2-byte aligned): ALIGNED stays false
+    const bool al = !half && (!d_out || aligned16(d_out)), be = !(flags & SML_FLAG_PAYLOAD_LE);
     // the reciprocal form is the fp32 output's, which needs the exponents
     const bool rcp = exps && (num_workers & (num_workers - 1)) == 0;
+    if (half && d_out) {
+        dispatch_packet(packet_numel, [&](auto Pc) {
+            dispatch_bools([&](auto BE, auto RCP, auto F16) {
+                // a bucket needs the exponents (checked above): EXPS is true
+                constexpr int kH = F16() ? kHalfF16 : kHalfBF16;
+                k_switch_aggregate<Pc(), false, BE(), RCP(), true, kH><<<grid, kBlockThreads, 0, st>>>(a);
+            }, be, rcp, dt == SML_FLOAT16);
+        });
+        return launch_check();
+    }
     dispatch_packet(packet_numel, [&](auto Pc) {
         dispatch_bools([&](auto AL, auto BE, auto RCP, auto EXPS) {
             // RCP without EXPS cannot occur (rcp above): not instantiated
@@ -313,6 +335,24 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
         }, al, be, rcp, exps);
     });
     return launch_check();
+}
+
+sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t* const* d_exps,
+                                  uint16_t num_workers, uint64_t numel, uint32_t packet_numel,
+                                  int32_t* d_payload_out, int8_t* d_exps_out, float* d_out,
+                                  uint32_t flags, void* stream) {
+    return switch_aggregate(d_payloads, d_exps, num_workers, numel, packet_numel, d_payload_out, d_exps_out, d_out,
+                            SML_FLOAT32, flags, stream);
+}
+
+sml_status_t sml_switch_aggregate_typed(const int32_t* const* d_payloads, const int8_t* const* d_exps,
+                                        uint16_t num_workers, uint64_t numel, uint32_t packet_numel,
+                                        int32_t* d_payload_out, int8_t* d_exps_out, void* d_out,
+                                        sml_data_type_t data_type, uint32_t flags, void* stream) {
+    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
+    if (data_type != SML_FLOAT32 && data_type != SML_FLOAT16 && data_type != SML_BFLOAT16) return SML_ERR_UNSUPPORTED;
+    return switch_aggregate(d_payloads, d_exps, num_workers, numel, packet_numel, d_payload_out, d_exps_out, d_out,
+                            data_type, flags, stream);
 }
 
 sml_status_t sml_switch_exps(const int8_t* const* d_exps, uint16_t num_workers, uint64_t num_blocks,

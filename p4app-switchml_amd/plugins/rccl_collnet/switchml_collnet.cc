@@ -117,6 +117,8 @@ bool g_trace = false;
 int type_size(ncclDataType_t t) {
     switch (t) {
         case ncclUint8: return 1;
+        case ncclFloat16:
+        case ncclBfloat16: return 2;
         case ncclInt32:
         case ncclFloat32: return 4;
         default: return 0;
@@ -245,8 +247,21 @@ ncclResult_t sml_connect(void* handles[], int nranks, int rank, void* listen_com
     return ncclSuccess;
 }
 
+// The started Context's configuration runs 16-bit float jobs.
+bool runs_half_types() {
+    switchml::Context& ctx = switchml::Context::GetInstance();
+    return ctx.GetContextState() == switchml::Context::RUNNING && ctx.GetConfig().RunsHalfTypes();
+}
+
 ncclResult_t sml_reduce_support(ncclDataType_t dtype, ncclRedOp_t op, int* supported) {
-    *supported = (dtype == ncclFloat32 || dtype == ncclInt32 || dtype == ncclUint8) && op == ncclSum;
+    // fp16 / bf16 need no widening buffer: the client's kernels convert — in
+    // the configurations that run them (Config::RunsHalfTypes).  Elsewhere
+    // (backend = xgmi, mode = packet) the answer stays 0, as before these
+    // types existed, so RCCL reduces such buckets with its own algorithms
+    // instead of posting jobs here that would end FAILED.
+    const bool half = dtype == ncclFloat16 || dtype == ncclBfloat16;
+    *supported = op == ncclSum && (dtype == ncclFloat32 || dtype == ncclInt32 || dtype == ncclUint8 ||
+                                   (half && runs_half_types()));
     return ncclSuccess;
 }
 
@@ -268,7 +283,10 @@ ncclResult_t sml_dereg_mr(void*, void* mhandle) {
 }
 
 void submit(Request* r) {
-    const switchml::DataType sdt = r->dtype == ncclFloat32 ? switchml::FLOAT32 : switchml::INT32;
+    const switchml::DataType sdt = r->dtype == ncclFloat32    ? switchml::FLOAT32
+                                   : r->dtype == ncclFloat16  ? switchml::FLOAT16
+                                   : r->dtype == ncclBfloat16 ? switchml::BFLOAT16
+                                                              : switchml::INT32;
     r->job = switchml::Context::GetInstance().AllReduceAsync(r->send, r->recv, (uint64_t)r->count, sdt,
                                                              switchml::SUM);
     g_calls.iallreduce_submitted++;
@@ -365,6 +383,9 @@ ncclResult_t sml_iallreduce(void* coll_comm, void* send, void* recv, int count, 
     if (op != ncclSum || type_size(dtype) == 0 || count < 0) return ncclInvalidArgument;
     switchml::Context& ctx = switchml::Context::GetInstance();
     if (ctx.GetContextState() != switchml::Context::RUNNING) return ncclInvalidUsage;
+    // a caller that ignored reduceSupport's 0: refused here, before a job
+    // exists that would fail and take the cross-rank job order with it
+    if ((dtype == ncclFloat16 || dtype == ncclBfloat16) && !runs_half_types()) return ncclInvalidArgument;
     auto* c = static_cast<CollComm*>(coll_comm);
     auto* r = new Request{nullptr, dtype, count, send, recv, recv, nullptr, nullptr, {}, false};
     std::lock_guard<std::mutex> lk(g_mu);

@@ -30,6 +30,9 @@ FLAG_PROCESS_PACKET = 0x8   # sml_exchange_burst: the dummy backend's ProcessPac
 
 PACKET_NUMELS = (64, 128, 256, 512, 1024)
 
+# sml_data_type_t
+FLOAT32, INT32, FLOAT16, BFLOAT16 = 0, 1, 2, 3
+
 _lib = None
 
 
@@ -151,6 +154,16 @@ def lib():
     L.sml_unpack_frames_int32.argtypes = [vp, u64, u64, u64, u32, u64, vp, vp, vp, vp]
     L.sml_switch_aggregate.restype = i32
     L.sml_switch_aggregate.argtypes = [vp, vp, u16, u64, u32, vp, vp, vp, u32, vp]
+    L.sml_exponents_typed.restype = i32
+    L.sml_exponents_typed.argtypes = [vp, i32, u64, u32, vp, vp]
+    L.sml_quantize_pack_typed.restype = i32
+    L.sml_quantize_pack_typed.argtypes = [vp, i32, u64, u32, u16, vp, vp, vp, u32, vp]
+    L.sml_dequantize_typed.restype = i32
+    L.sml_dequantize_typed.argtypes = [vp, vp, u64, u32, u16, vp, i32, u32, vp]
+    L.sml_roundtrip_loopback_typed.restype = i32
+    L.sml_roundtrip_loopback_typed.argtypes = [vp, vp, i32, u64, u32, u16, vp, vp, u32, vp]
+    L.sml_switch_aggregate_typed.restype = i32
+    L.sml_switch_aggregate_typed.argtypes = [vp, vp, u16, u64, u32, vp, vp, vp, i32, u32, vp]
     L.sml_copy_segments.restype = i32
     L.sml_copy_segments.argtypes = [vp, vp, vp, u32, u32, vp]
     L.sml_switch_exps.restype = i32
@@ -286,6 +299,16 @@ def _dev(t, dtype, name):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _float_type(dtype, name):
+    """sml_data_type_t of a float bucket's torch dtype: fp32, or one of the
+    16-bit types the kernels convert (the sml_*_typed entry points)."""
+    torch = _torch()
+    code = {torch.float32: FLOAT32, torch.float16: FLOAT16, torch.bfloat16: BFLOAT16}.get(dtype)
+    if code is None:
+        raise TypeError(f"{name} must be float32, float16 or bfloat16, got {dtype}")
+    return code
+
+
 def scale_lut(num_workers: int):
     import numpy as np
     out = np.empty(256, dtype=np.float32)
@@ -305,6 +328,11 @@ def exponents(x, packet_numel: int = 256, out=None, stream=None):
     B = num_blocks(x.numel(), packet_numel)
     if out is None:
         out = torch.empty(B, dtype=torch.int8, device=x.device)
+    dt = _float_type(x.dtype, "x")
+    if dt != FLOAT32:
+        _check("sml_exponents_typed", lib().sml_exponents_typed(
+            _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, _dev(out, torch.int8, "exps"), _stream(stream, x)))
+        return out
     _check("sml_exponents", lib().sml_exponents(_dev(x, torch.float32, "x"), x.numel(), packet_numel,
                                                 _dev(out, torch.int8, "exps"), _stream(stream, x)))
     return out
@@ -312,7 +340,9 @@ def exponents(x, packet_numel: int = 256, out=None, stream=None):
 
 def quantize_pack(x, packet_numel: int = 256, num_workers: int = 1, global_exps=None,
                   payload=None, exps_out=None, want_exps: bool = True, flags: int = 0, stream=None):
-    """Returns (payload int32[B*P] (BE words unless FLAG_PAYLOAD_LE), exps int8[B] or None)."""
+    """Returns (payload int32[B*P] (BE words unless FLAG_PAYLOAD_LE), exps int8[B] or None).
+    `x` is fp32, or fp16 / bf16 (widened inside the kernel: the planes are
+    those of x.float())."""
     torch = _torch()
     B = num_blocks(x.numel(), packet_numel)
     if payload is None:
@@ -321,9 +351,15 @@ def quantize_pack(x, packet_numel: int = 256, num_workers: int = 1, global_exps=
         exps_out = torch.empty(B, dtype=torch.int8, device=x.device)
     g = None if global_exps is None else _dev(global_exps, torch.int8, "global_exps")
     e = None if exps_out is None else _dev(exps_out, torch.int8, "exps_out")
-    _check("sml_quantize_pack", lib().sml_quantize_pack(
-        _dev(x, torch.float32, "x"), x.numel(), packet_numel, num_workers, g,
-        _dev(payload, torch.int32, "payload"), e, flags, _stream(stream, x)))
+    dt = _float_type(x.dtype, "x")
+    if dt != FLOAT32:
+        _check("sml_quantize_pack_typed", lib().sml_quantize_pack_typed(
+            _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, num_workers, g,
+            _dev(payload, torch.int32, "payload"), e, flags, _stream(stream, x)))
+    else:
+        _check("sml_quantize_pack", lib().sml_quantize_pack(
+            _dev(x, torch.float32, "x"), x.numel(), packet_numel, num_workers, g,
+            _dev(payload, torch.int32, "payload"), e, flags, _stream(stream, x)))
     return payload, (global_exps if global_exps is not None else exps_out)
 
 
@@ -340,24 +376,38 @@ def quantize_pack_launcher(x, packet_numel: int, num_workers: int, payload, exps
         raise ValueError(f"payload must hold B*P = {B * packet_numel} words")
     if exps_out is not None and exps_out.numel() != B:
         raise ValueError(f"exps_out must hold B = {B} bytes")
-    args = (_dev(x, torch.float32, "x"), x.numel(), packet_numel, num_workers,
+    dt = _float_type(x.dtype, "x")
+    args = (x.numel(), packet_numel, num_workers,
             None if global_exps is None else _dev(global_exps, torch.int8, "global_exps"),
             _dev(payload, torch.int32, "payload"),
             None if exps_out is None else _dev(exps_out, torch.int8, "exps_out"), flags, _stream(stream, x))
-    fn = lib().sml_quantize_pack
+    if dt != FLOAT32:
+        name, fn, args = "sml_quantize_pack_typed", lib().sml_quantize_pack_typed, (_dev(x, x.dtype, "x"), dt) + args
+    else:
+        name, fn, args = "sml_quantize_pack", lib().sml_quantize_pack, (_dev(x, torch.float32, "x"),) + args
 
     def launch():
         s = fn(*args)
         if s != SML_OK:
-            raise SwitchMLError("sml_quantize_pack", s)
+            raise SwitchMLError(name, s)
     return launch
 
 
 def dequantize(payload, exps, numel: int, packet_numel: int = 256, num_workers: int = 1,
-               out=None, flags: int = 0, stream=None):
+               out=None, flags: int = 0, stream=None, out_dtype=None):
+    """K4 into `out`, or into a new bucket of `out_dtype` (default fp32; fp16 /
+    bf16: the fp32 result narrowed inside the kernel, round to nearest even)."""
     torch = _torch()
     if out is None:
-        out = torch.empty(numel, dtype=torch.float32, device=payload.device)
+        out = torch.empty(numel, dtype=out_dtype or torch.float32, device=payload.device)
+    elif out_dtype is not None and out.dtype != out_dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype {out_dtype}")
+    dt = _float_type(out.dtype, "out")
+    if dt != FLOAT32:
+        _check("sml_dequantize_typed", lib().sml_dequantize_typed(
+            _dev(payload, torch.int32, "payload"), _dev(exps, torch.int8, "exps"), numel, packet_numel,
+            num_workers, _dev(out, out.dtype, "out"), dt, flags, _stream(stream, payload)))
+        return out
     _check("sml_dequantize", lib().sml_dequantize(
         _dev(payload, torch.int32, "payload"), _dev(exps, torch.int8, "exps"), numel, packet_numel,
         num_workers, _dev(out, torch.float32, "out"), flags, _stream(stream, payload)))
@@ -387,6 +437,12 @@ def roundtrip_loopback(x, packet_numel: int = 256, num_workers: int = 1, out=Non
         out = torch.empty_like(x)
     p = None if payload is None else _dev(payload, torch.int32, "payload")
     e = None if exps_out is None else _dev(exps_out, torch.int8, "exps_out")
+    dt = _float_type(x.dtype, "x")
+    if dt != FLOAT32:   # fp16 / bf16 in, the same type out
+        _check("sml_roundtrip_loopback_typed", lib().sml_roundtrip_loopback_typed(
+            _dev(x, x.dtype, "x"), _dev(out, x.dtype, "out"), dt, x.numel(), packet_numel,
+            num_workers, p, e, flags, _stream(stream, x)))
+        return out
     _check("sml_roundtrip_loopback", lib().sml_roundtrip_loopback(
         _dev(x, torch.float32, "x"), _dev(out, torch.float32, "out"), x.numel(), packet_numel,
         num_workers, p, e, flags, _stream(stream, x)))
@@ -422,14 +478,15 @@ MAX_SWITCH_WORKERS = 16
 
 
 def switch_aggregate(payloads, exps=None, numel: int | None = None, packet_numel: int = 256,
-                     payload_out=None, exps_out=None, out=None, flags: int = 0, stream=None):
+                     payload_out=None, exps_out=None, out=None, flags: int = 0, stream=None, out_dtype=None):
     """K6: the switch's per-slot aggregation over W worker planes, fused with
     the dequantize (p4/processor.p4:48-54 wrapping bit<32> sum,
     p4/exponents.p4:48-54 signed int8 max, then PostprocessSingle with
     scale(W, e_max), ppp.cc:197-251).  `payloads`: W int32 planes of B*P
     words (BE unless FLAG_PAYLOAD_LE); `exps`: W int8 planes of B bytes.
     Writes whichever of payload_out / exps_out / out is given; with none
-    given, returns a new fp32 bucket `out` of `numel` elements."""
+    given, returns a new bucket `out` of `numel` elements of `out_dtype`
+    (default fp32; fp16 / bf16, or a typed `out`: narrowed inside the kernel)."""
     torch = _torch()
     W = len(payloads)
     if W == 0 or W > MAX_SWITCH_WORKERS:
@@ -445,13 +502,24 @@ def switch_aggregate(payloads, exps=None, numel: int | None = None, packet_numel
     if exps is not None:
         if len(exps) != W or any(e.numel() != B for e in exps):
             raise ValueError("need one exponent plane of B bytes per payload plane")
-    if payload_out is None and exps_out is None and out is None:
-        out = torch.empty(numel, dtype=torch.float32, device=payloads[0].device)
+    if out is None and (out_dtype is not None or (payload_out is None and exps_out is None)):
+        out = torch.empty(numel, dtype=out_dtype or torch.float32, device=payloads[0].device)
+    elif out is not None and out_dtype is not None and out.dtype != out_dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype {out_dtype}")
+    dt = FLOAT32 if out is None else _float_type(out.dtype, "out")
     # planes are int32 tensors, or (peer-to-peer switch) mapped peer planes
     # exposing data_ptr()/numel() only
     pp = (ctypes.c_void_p * W)(*[_dev(p, torch.int32, "payloads[w]").value if isinstance(p, torch.Tensor)
                                  else p.data_ptr() for p in payloads])
     ep = None if exps is None else (ctypes.c_void_p * W)(*[_dev(e, torch.int8, "exps[w]").value for e in exps])
+    if dt != FLOAT32:
+        _check("sml_switch_aggregate_typed", lib().sml_switch_aggregate_typed(
+            ctypes.cast(pp, ctypes.c_void_p), None if ep is None else ctypes.cast(ep, ctypes.c_void_p), W, numel,
+            packet_numel,
+            None if payload_out is None else _dev(payload_out, torch.int32, "payload_out"),
+            None if exps_out is None else _dev(exps_out, torch.int8, "exps_out"),
+            _dev(out, out.dtype, "out"), dt, flags, _stream(stream, payloads[0])))
+        return out
     _check("sml_switch_aggregate", lib().sml_switch_aggregate(
         ctypes.cast(pp, ctypes.c_void_p), None if ep is None else ctypes.cast(ep, ctypes.c_void_p), W, numel,
         packet_numel,

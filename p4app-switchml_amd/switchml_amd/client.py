@@ -12,7 +12,7 @@ from . import lib as _kernel_lib
 
 CREATED, STARTING, RUNNING, STOPPING, STOPPED = range(5)
 JOB_INIT, JOB_QUEUED, JOB_RUNNING, JOB_FINISHED, JOB_FAILED = range(5)
-FLOAT32, INT32 = 0, 1
+FLOAT32, INT32, FLOAT16, BFLOAT16 = 0, 1, 2, 3
 SUM = 0
 
 _bound = False
@@ -109,6 +109,10 @@ def _dtype_of(t):
         return FLOAT32
     if s.endswith("int32"):
         return INT32
+    if s.endswith("bfloat16"):            # before float16: the name ends with it too
+        return BFLOAT16
+    if s.endswith("float16"):             # torch.float16, numpy.float16
+        return FLOAT16
     raise TypeError(f"unsupported dtype {t.dtype}")
 
 

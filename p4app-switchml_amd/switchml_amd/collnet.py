@@ -26,6 +26,7 @@ LOGGER = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_ulong, ctypes.c_char_p, c
 
 # ncclDataType_t / ncclRedOp_t values (nccl.h)
 NCCL_UINT8, NCCL_INT32, NCCL_FLOAT32, NCCL_FLOAT64 = 1, 2, 7, 8
+NCCL_FLOAT16, NCCL_BFLOAT16 = 6, 9   # converted inside the client's kernels (no widening buffer)
 NCCL_SUM, NCCL_MAX = 0, 2
 
 
