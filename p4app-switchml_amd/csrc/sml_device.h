@@ -1,6 +1,7 @@
 // sml_device.h — device-side building blocks shared by the gfx950 kernels of
-// SwitchML's end-host pre/post-processor (sml_quantizer.hip: planes;
-// sml_frames.hip: DPDK frames).
+// SwitchML's end-host pre/post-processor (sml_planes.h: the plane kernel
+// templates, sml_quantizer.hip: fp32 planes, sml_half.hip: 16-bit planes;
+// sml_frames.hip: DPDK frames; sml_switch.hip: the in-node switch).
 //
 // What the reference does per 1 KiB LTU on one CPU thread
 // (client_lib/src/prepostprocessors/cpu_exponent_quantizer_ppp.cc, "ppp.cc"),
@@ -134,6 +135,32 @@ __device__ __forceinline__ float dequantize1(uint32_t q_host_order, float s) {
 
 __device__ __forceinline__ uint32_t bswap(uint32_t v) { return __builtin_bswap32(v); }
 
+// PostprocessSingle's per-word arithmetic on a host-order word: divided by the
+// scale s, or (RCP, power-of-two W) multiplied by its exact reciprocal s.
+template <bool RCP>
+__device__ __forceinline__ float dequant1(uint32_t q, float s) {
+    if constexpr (RCP) return (float)(int32_t)q * s;
+    else return dequantize1(q, s);
+}
+
+// Four words of the wire: ntohl (BE), then dequant1.
+template <bool BE, bool RCP>
+__device__ __forceinline__ f4 dequant_words(u4 w, float s) {
+    uint32_t q0 = (uint32_t)w.x, q1 = (uint32_t)w.y, q2 = (uint32_t)w.z, q3 = (uint32_t)w.w;
+    if constexpr (BE) { q0 = bswap(q0); q1 = bswap(q1); q2 = bswap(q2); q3 = bswap(q3); }
+    return mkf4(dequant1<RCP>(q0, s), dequant1<RCP>(q1, s), dequant1<RCP>(q2, s), dequant1<RCP>(q3, s));
+}
+
+// VCL body end of the block holding idx: the first n - n % 16 elements of the
+// block round to nearest even; only the last (partial) block has a scalar
+// half-away tail.
+template <int P>
+__device__ __forceinline__ uint64_t vcl_body(uint64_t idx, uint64_t numel) {
+    const uint64_t blk0 = idx / P * P;
+    const uint64_t n = numel - blk0 < (uint64_t)P ? numel - blk0 : (uint64_t)P;
+    return blk0 + (n - n % 16);
+}
+
 // ------------------------------------------------------------- memory ops
 
 // ALIGNED = false: slices that start at any 4-byte offset (FIFO slices,
@@ -213,8 +240,9 @@ __device__ __forceinline__ void store4_guarded(float* p, f4 v, uint64_t idx, uin
 }
 
 // ------------------------------------------------ 16-bit float elements
-// FLOAT16 / BFLOAT16 job slices (sml_half.hip): the element is widened to
-// fp32 in registers right after the load and narrowed right before the store,
+// FLOAT16 / BFLOAT16 job slices (Elem16 below, sml_half.hip): the element is
+// widened to fp32 in registers right after the load and narrowed right before
+// the store,
 // everything between is the fp32 arithmetic above.  H is the sml_data_type_t
 // value: 2 = IEEE binary16, 3 = bfloat16; elements travel as raw uint16_t.
 constexpr int kHalfF16 = 2;
@@ -276,6 +304,39 @@ __device__ __forceinline__ void store4h_guarded(uint16_t* p, f4 v, uint64_t idx,
     if (idx + 2 < numel) p[2] = narrow16<H>(v.z);
     if (idx + 3 < numel) p[3] = narrow16<H>(v.w);
 }
+
+// Element policies: what a plane kernel needs to know about its element type
+// (the kernel templates of sml_planes.h take one as E).  fp32 keeps its
+// ALIGNED axis (16-byte or any 4-byte alignment); a 16-bit slice has one form.
+template <bool ALIGNED>
+struct ElemF32 {
+    typedef float raw;
+    static constexpr int kBytes = 4;
+    static __device__ __forceinline__ f4 load4(const raw* p) { return sml::load4<ALIGNED>(p); }
+    static __device__ __forceinline__ f4 load4_guarded(const raw* p, uint64_t idx, uint64_t numel) {
+        return sml::load4_guarded(p, idx, numel);
+    }
+    template <bool NT>
+    static __device__ __forceinline__ void store4(raw* p, f4 v) { sml::store4<ALIGNED, NT>(p, v); }
+    static __device__ __forceinline__ void store4_guarded(raw* p, f4 v, uint64_t idx, uint64_t numel) {
+        sml::store4_guarded(p, v, idx, numel);
+    }
+};
+
+template <int H>
+struct Elem16 {
+    typedef uint16_t raw;
+    static constexpr int kBytes = 2;
+    static __device__ __forceinline__ f4 load4(const raw* p) { return load4h<H>(p); }
+    static __device__ __forceinline__ f4 load4_guarded(const raw* p, uint64_t idx, uint64_t numel) {
+        return load4h_guarded<H>(p, idx, numel);
+    }
+    template <bool NT>
+    static __device__ __forceinline__ void store4(raw* p, f4 v) { store4h<H, NT>(p, v); }
+    static __device__ __forceinline__ void store4_guarded(raw* p, f4 v, uint64_t idx, uint64_t numel) {
+        store4h_guarded<H>(p, v, idx, numel);
+    }
+};
 
 // Payload stores keep the default cache policy: measured 9 % faster than
 // non-temporal stores on the 256 MiB bucket (loads stay non-temporal,
@@ -476,8 +537,9 @@ __device__ __forceinline__ uint64_t xcd_block(uint32_t C) {
 }
 
 
+template <class T>
 struct QuantArgs {
-    const float* in;
+    const T* in;
     uint64_t numel;
     uint64_t nblocks;       // B
     uint64_t ntiles;        // ceil(B*P / tile_elems<U>())
@@ -488,16 +550,18 @@ struct QuantArgs {
     uint32_t xcd;           // xcd_block chunk (0 = plain order)
 };
 
-template <bool ALIGNED, int U>
-__device__ __forceinline__ void load_tile(const QuantArgs& a, uint64_t base, int lane, f4 (&v)[U]) {
+// The loads of one tile of a.in (QuantArgs, RoundTripArgs): whole vectors
+// inside the slice, element by element in its last tile.
+template <class E, int U, class A>
+__device__ __forceinline__ void load_tile(const A& a, uint64_t base, int lane, f4 (&v)[U]) {
     if (base + tile_elems<U>() <= a.numel) {
 #pragma unroll
-        for (int u = 0; u < U; u++) v[u] = load4<ALIGNED>(a.in + base + (u * kWave + lane) * 4);
+        for (int u = 0; u < U; u++) v[u] = E::load4(a.in + base + (u * kWave + lane) * 4);
     } else {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-            v[u] = load4_guarded(a.in + idx, idx, a.numel);
+            v[u] = E::load4_guarded(a.in + idx, idx, a.numel);
         }
     }
 }

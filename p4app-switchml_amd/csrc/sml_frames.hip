@@ -94,18 +94,18 @@ void k_quantize_frames(FrameArgs a) {
 #pragma unroll
     for (int i = 1; i < 11; i++) hconst = hd == i ? a.hdr[i] : hconst;
     const uint32_t m2 = 2u * a.mop;
-    QuantArgs qa;                                          // reuse the K1 tile loader
+    QuantArgs<float> qa;                                   // reuse the K1 tile loader
     qa.in = a.in;
     qa.numel = a.numel;
     // As K1: the first tile's loads go out before the scale table is built.
     uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index();
     f4 v[kU];
-    if (t < a.ntiles) load_tile<ALIGNED>(qa, t * kTileElems, lane, v);
+    if (t < a.ntiles) load_tile<ElemF32<ALIGNED>>(qa, t * kTileElems, lane, v);
     if constexpr (!I32) build_lut(lut, a.W);
     for (bool first = true; t < a.ntiles; t += nwaves, first = false) {
         const uint64_t base = t * kTileElems;
         const uint64_t pk0 = base / P;                     // first block of the tile
-        if (!first) load_tile<ALIGNED>(qa, base, lane, v); // later tiles (grid-stride)
+        if (!first) load_tile<ElemF32<ALIGNED>>(qa, base, lane, v); // later tiles (grid-stride)
         int eloc[kU];
         if constexpr (I32) {
 #pragma unroll

@@ -1,13 +1,14 @@
 // sml_quantizer.hip — CDNA4 (gfx950) kernels for the planes of SwitchML's
 // end-host pre/post-processor (CpuExponentQuantizerPPP,
 // client_lib/src/prepostprocessors/cpu_exponent_quantizer_ppp.cc = "ppp.cc")
-// and their C-ABI entry points (include/switchml_hip.h): K1 fused exponent +
+// and their C-ABI entry points (include/switchml_hip.h): the fp32
+// instantiations of the plane kernels of sml_planes.h (K1 fused exponent +
 // quantize + pack, K2 exponents, K3 quantize with given exponents, K4
-// dequantize, the fused loopback round trip, the word streams (loopback x W,
-// INT32 byteswap), RDMA immediates and the copy probe.  Tile layout, numerics
-// and parity notes: sml_device.h; DPDK frames: sml_frames.hip.
-#include "sml_host.h"
-
+// dequantize, the fused loopback round trip), the batched round trip, the word
+// streams (loopback x W, INT32 byteswap), RDMA immediates and the copy probe.
+// Tile layout, numerics and parity notes: sml_device.h; 16-bit slices:
+// sml_half.hip; DPDK frames: sml_frames.hip.
+#include "sml_planes.h"
 
 namespace sml {
 
@@ -16,293 +17,6 @@ std::atomic<uint32_t> g_grid_limit{0};
 std::atomic<uint32_t> g_xcd_chunk{64};
 
 // -------------------------------------------------------------- kernels
-
-// K3: the tile's global exponents (one scalar load per slice when aligned).
-template <int P, int U>
-__device__ __forceinline__ void global_tile_exponents(const QuantArgs& a, uint64_t base, int lane, int (&e)[U]) {
-    if (base + tile_elems<U>() <= a.nblocks * P && slice_exps_scalar_ok<P>(a.gexp)) {
-#pragma unroll
-        for (int u = 0; u < U; u++) e[u] = (int)(int8_t)slice_exponent_byte<P>(a.gexp, base, u, lane);
-    } else {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            uint64_t pkt = (base + (uint64_t)(u * kWave + lane) * 4) / P;
-            e[u] = pkt < a.nblocks ? (int)a.gexp[pkt] : 0;
-        }
-    }
-}
-
-// Quantize + pack 4 consecutive elements (one lane's part of a slice).
-template <int P, bool BE, bool RNE, bool NTS>
-__device__ __forceinline__ void quant_slice(const QuantArgs& a, uint64_t idx, f4 v, const float* lut, int e) {
-    const float s = lut[(uint8_t)e];
-    uint64_t body = 0;
-    if constexpr (RNE) {
-        // VCL body = first n - n%16 elements of the block; only the last
-        // (partial) block has a scalar half-away tail.
-        const uint64_t blk0 = idx / P * P;
-        const uint64_t n = a.numel - blk0 < (uint64_t)P ? a.numel - blk0 : (uint64_t)P;
-        body = blk0 + (n - n % 16);
-    }
-    u4 q = quantize4<RNE>(v, s, idx, body);
-    if constexpr (BE) { q.x = bswap(q.x); q.y = bswap(q.y); q.z = bswap(q.z); q.w = bswap(q.w); }
-    store_payload_as<NTS>(a.payload + idx / 4, q);
-}
-
-// Exponents, quantize and pack of one loaded tile (K3: `e` holds the global
-// exponents already).
-template <int P, bool GLOBAL, bool BE, bool RNE, int U, bool NTS>
-__device__ __forceinline__ void quant_tile(const QuantArgs& a, uint64_t base, int lane, const f4 (&v)[U],
-                                           const float* lut, int (&e)[U]) {
-    const uint64_t padded = a.nblocks * P;
-    constexpr int kElems = tile_elems<U>();
-    if constexpr (!GLOBAL) {
-        tile_exponents<P>(v, e);
-        if (a.exps_out) {
-            constexpr int kPk = kElems / P;       // packets per tile
-            if (((uintptr_t)a.exps_out & (kPk - 1)) == 0 && base + kElems <= padded) {
-                store_tile_exponents<P>(a.exps_out + base / P, lane, e);
-            } else {
-                store_exponents<P>(a.exps_out, base, lane, e, a.nblocks);
-            }
-        }
-    }
-    if (!a.payload) return;
-    // A tile inside the padded plane takes a branch-free slice loop.  With a
-    // per-slice `continue` here, hipcc's wait-count pass sees paths that skip
-    // a slice and waits vmcnt(0) at the top of EVERY slice — i.e. on the
-    // previous slice's store as well — which cost K3 (whose first use of the
-    // loaded data is inside this loop) 3 % against K1 (whose exponent reduce
-    // consumes all four slices first): profiles/r02/k1_vs_k3_counters.json,
-    // ab_k3_waitcnt.json.
-    if (base + kElems <= padded) {
-#pragma unroll
-        for (int u = 0; u < U; u++) quant_slice<P, BE, RNE, NTS>(a, base + (uint64_t)(u * kWave + lane) * 4, v[u], lut, e[u]);
-        return;
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-        if (idx < padded) quant_slice<P, BE, RNE, NTS>(a, idx, v[u], lut, e[u]);
-    }
-}
-
-// K1 (fused exponent + quantize + pack), K2 (exponents only: payload == nullptr)
-// and K3 (given global exponents: GLOBAL = true).  A wave's tile is U slices
-// of 256 elements (one 16-B load per lane per slice, all issued before any
-// arithmetic); U = 4 by default — four loads in flight per lane keep the
-// stream at the copy rate, smaller tiles measured slower.
-template <int P, bool ALIGNED, bool GLOBAL, bool BE, bool RNE, int U, bool NTS = false>
-__global__ __launch_bounds__(kBlockThreads) void k_quantize_pack(QuantArgs a) {
-    __shared__ float lut[256];
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
-    // The wave's first tile is loaded BEFORE the workgroup builds its scale
-    // table: the table and its barrier run while the loads are in flight (a
-    // plain s_barrier does not wait for them), instead of delaying the first
-    // HBM request of every workgroup of the one-shot grid: K1 +1.1 / +1.7 %
-    // at 256 / 128 MiB (profiles/r04/ab_lut_early.json).
-    uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index();
-    f4 v[U];
-    if (t < a.ntiles) load_tile<ALIGNED>(a, t * tile_elems<U>(), lane, v);
-    if (a.payload) build_lut(lut, a.W);
-    while (t < a.ntiles) {
-        const uint64_t base = t * tile_elems<U>();
-        int e[U];
-        // K3: the exponent dword is read after the data loads are in flight
-        if constexpr (GLOBAL) global_tile_exponents<P>(a, base, lane, e);
-        quant_tile<P, GLOBAL, BE, RNE, U, NTS>(a, base, lane, v, lut, e);
-        t += nwaves;
-        if (t < a.ntiles) load_tile<ALIGNED>(a, t * tile_elems<U>(), lane, v);
-    }
-}
-
-// ntohl (BE) -> int -> float, divided by the scale (or multiplied by its
-// exact reciprocal, RCP) — PostprocessSingle's per-element arithmetic.
-template <bool BE, bool RCP>
-__device__ __forceinline__ f4 dequant_words(u4 w, float s) {
-    uint32_t q0 = (uint32_t)w.x, q1 = (uint32_t)w.y, q2 = (uint32_t)w.z, q3 = (uint32_t)w.w;
-    if constexpr (BE) { q0 = bswap(q0); q1 = bswap(q1); q2 = bswap(q2); q3 = bswap(q3); }
-    if constexpr (RCP)
-        return mkf4((float)(int32_t)q0 * s, (float)(int32_t)q1 * s, (float)(int32_t)q2 * s, (float)(int32_t)q3 * s);
-    else
-        return mkf4(dequantize1(q0, s), dequantize1(q1, s), dequantize1(q2, s), dequantize1(q3, s));
-}
-
-struct DequantArgs {
-    const u4* payload;
-    const int8_t* exps;
-    float* out;
-    uint64_t numel;
-    uint64_t ntiles;        // ceil(numel / 1024)
-    uint32_t W;
-    uint32_t xcd;           // xcd_block chunk (0 = plain order)
-};
-
-// K4: dequantize the aggregated payload (PostprocessSingle, ppp.cc:197-251).
-// RCP (power-of-two W): multiply by the exact reciprocal instead of the IEEE
-// division — same bits (rcp_scale_pow2).
-template <int P, bool ALIGNED, bool BE, bool RCP, bool NT = false, int U = kU>
-__global__ __launch_bounds__(kBlockThreads) void k_dequantize(DequantArgs a) {
-    __shared__ float lut[256];
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
-    constexpr int kElems = tile_elems<U>();
-    uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index();
-    if constexpr (RCP) build_rcp_lut(lut, a.W);
-    else build_lut(lut, a.W);
-    for (; t < a.ntiles; t += nwaves) {
-        const uint64_t base = t * kElems;
-        const bool full = base + kElems <= a.numel;
-        u4 w[U];
-        float s[U];
-        if (full && slice_exps_scalar_ok<P>(a.exps)) {
-            // Full tile: each slice's exponent bytes with one scalar load
-            // (measured: a per-lane byte load per slice costs ~8 % at
-            // P != 256), then a branch-free slice loop — shared per-slice
-            // blocks with the partial-tile path made hipcc wait vmcnt(0), on
-            // the previous slice's store too, before every slice.
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                w[u] = __builtin_nontemporal_load(a.payload + (base + (uint64_t)(u * kWave + lane) * 4) / 4);
-                s[u] = lut[slice_exponent_byte<P>(a.exps, base, u, lane)];
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-                store4<ALIGNED, NT>(a.out + idx, dequant_words<BE, RCP>(w[u], s[u]));
-            }
-            continue;
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-                if (full || idx < a.numel) {
-                    w[u] = __builtin_nontemporal_load(a.payload + idx / 4);
-                    s[u] = lut[(uint8_t)a.exps[idx / P]];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-            if (!full && idx >= a.numel) continue;
-            const f4 o = dequant_words<BE, RCP>(w[u], s[u]);
-            if (full) store4<ALIGNED, NT>(a.out + idx, o);
-            else store4_guarded(a.out + idx, o, idx, a.numel);
-        }
-    }
-}
-
-struct RoundTripArgs {
-    const float* in;
-    float* out;
-    uint64_t numel;
-    uint64_t nblocks;
-    uint64_t ntiles;        // ceil(B*P / 1024)
-    u4* payload;          // nullable: on-wire plane as sent
-    int8_t* exps_out;       // nullable
-    uint32_t W;
-    uint32_t xcd;           // xcd_block chunk (0 = plain order)
-};
-
-// Fused dummy-backend round trip: PreprocessSingle -> ProcessPacket (x W) ->
-// PostprocessSingle for every packet of the slice in one HBM pass.  One tile
-// of one slice (blocks restart at the slice start, as in the reference):
-// roundtrip_load issues the tile's loads, roundtrip_compute does the rest.
-template <bool ALIGNED, int U>
-__device__ __forceinline__ void roundtrip_load(const RoundTripArgs& a, uint64_t t, int lane, f4 (&v)[U]) {
-    constexpr int kElems = tile_elems<U>();
-    const uint64_t base = t * kElems;
-    if (base + kElems <= a.numel) {
-#pragma unroll
-        for (int u = 0; u < U; u++) v[u] = load4<ALIGNED>(a.in + base + (u * kWave + lane) * 4);
-    } else {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-            v[u] = load4_guarded(a.in + idx, idx, a.numel);
-        }
-    }
-}
-
-template <int P, bool ALIGNED, bool BE, bool RNE, bool NT, int U>
-__device__ __forceinline__ void roundtrip_compute(const RoundTripArgs& a, uint64_t t, const float* lut, int lane,
-                                                  const f4 (&v)[U]) {
-    static_assert(U * 256 >= P, "a tile holds whole packets");
-    constexpr int kElems = tile_elems<U>();
-    const bool pow2 = (a.W & (a.W - 1)) == 0;
-    const uint32_t log2W = 31 - __builtin_clz(a.W);
-    const uint64_t padded = a.nblocks * P;
-    const uint64_t base = t * kElems;
-    const bool full = base + kElems <= a.numel;
-    int e[U];
-    tile_exponents<P>(v, e);
-    if (a.exps_out) {
-        constexpr int kPk = kElems / P;
-        if (((uintptr_t)a.exps_out & (kPk - 1)) == 0 && base + kElems <= padded)
-            store_tile_exponents<P>(a.exps_out + base / P, lane, e);
-        else
-            store_exponents<P>(a.exps_out, base, lane, e, a.nblocks);
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-        if (idx >= padded) continue;
-        const float s = lut[(uint8_t)e[u]];
-        uint64_t body = 0;
-        if constexpr (RNE) {
-            const uint64_t blk0 = idx / P * P;
-            const uint64_t n = a.numel - blk0 < (uint64_t)P ? a.numel - blk0 : (uint64_t)P;
-            body = blk0 + (n - n % 16);
-        }
-        const u4 qv = quantize4<RNE>(v[u], s, idx, body);
-        const uint32_t q[4] = {qv.x, qv.y, qv.z, qv.w};
-        if (a.payload) {
-            u4 wq = BE ? mku4(bswap(q[0]), bswap(q[1]), bswap(q[2]), bswap(q[3]))
-                          : mku4(q[0], q[1], q[2], q[3]);
-            store_payload(a.payload + idx / 4, wq);
-        }
-        // DummyBackend::ProcessPacket: int32 wrap multiply by W; then the
-        // dequantize (exact reciprocal multiply for power-of-two W, as K4).
-        f4 o;
-        if (pow2) {
-            const float r = rcp_scale_pow2(log2W, e[u]);
-            o = mkf4((float)(int32_t)(q[0] * a.W) * r, (float)(int32_t)(q[1] * a.W) * r,
-                     (float)(int32_t)(q[2] * a.W) * r, (float)(int32_t)(q[3] * a.W) * r);
-        } else {
-            o = mkf4(dequantize1(q[0] * a.W, s), dequantize1(q[1] * a.W, s), dequantize1(q[2] * a.W, s),
-                     dequantize1(q[3] * a.W, s));
-        }
-        if (full) store4<ALIGNED, NT>(a.out + idx, o);
-        else if (idx < a.numel) store4_guarded(a.out + idx, o, idx, a.numel);
-    }
-}
-
-template <int P, bool ALIGNED, bool BE, bool RNE, bool NT = false, int U = kU>
-__device__ __forceinline__ void roundtrip_tile(const RoundTripArgs& a, uint64_t t, const float* lut, int lane) {
-    f4 v[U];
-    roundtrip_load<ALIGNED, U>(a, t, lane, v);
-    roundtrip_compute<P, ALIGNED, BE, RNE, NT, U>(a, t, lut, lane, v);
-}
-
-template <int P, bool ALIGNED, bool BE, bool RNE, bool NT = false, int U = kU>
-__global__ __launch_bounds__(kBlockThreads) void k_roundtrip(RoundTripArgs a) {
-    __shared__ float lut[256];
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
-    uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index();
-    // As K1: the first tile's loads go out before the scale table is built
-    // (measured level here, +0.1-0.3 %: profiles/r04/ab_lut_early2.json).
-    f4 v[U];
-    if (t < a.ntiles) roundtrip_load<ALIGNED, U>(a, t, lane, v);
-    build_lut(lut, a.W);
-    while (t < a.ntiles) {
-        roundtrip_compute<P, ALIGNED, BE, RNE, NT, U>(a, t, lut, lane, v);
-        t += nwaves;
-        if (t < a.ntiles) roundtrip_load<ALIGNED, U>(a, t, lane, v);
-    }
-}
 
 // The fused round trip over a batch of slices (of one or several jobs) in ONE
 // launch: the slices' tiles are numbered consecutively (tile_end[s] = tiles of
@@ -335,7 +49,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_roundtrip_batch(RoundTripBatc
             else lo = mid + 1;
         }
         const uint32_t t0 = lo ? a.tile_end[lo - 1] : 0u;
-        RoundTripArgs r;
+        RoundTripArgs<float> r;
         r.in = a.in[lo];
         r.out = a.out[lo];
         r.numel = a.numel[lo];
@@ -345,7 +59,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_roundtrip_batch(RoundTripBatc
         r.exps_out = nullptr;
         r.W = a.W;
         r.xcd = a.xcd;
-        roundtrip_tile<P, false, true, RNE, NT, U>(r, t - t0, lut, lane);
+        roundtrip_tile<P, ElemF32<false>, true, RNE, NT, U>(r, t - t0, lut, lane);
     }
 }
 
@@ -460,6 +174,13 @@ static uint32_t quant_slices(uint32_t P) {
     return want > need ? want : need;
 }
 
+// K1 / K2 / K3 on an fp32 slice: the aligned form when the slice allows it.
+static sml_status_t quantize_f32(const float* d_in, uint64_t numel, uint32_t P, uint16_t W, const int8_t* d_gexp,
+                                 int32_t* d_payload, int8_t* d_exps_out, uint32_t flags, void* stream) {
+    return plane_quantize<ElemF32, 1, 2, 4>(d_in, aligned16(d_in), quant_slices(P), numel, P, W, d_gexp, d_payload,
+                                            d_exps_out, flags, stream);
+}
+
 }  // namespace sml
 
 using namespace sml;
@@ -521,53 +242,10 @@ sml_status_t sml_scale_lut_device(uint16_t num_workers, float* d_lut, void* stre
     return launch_check();
 }
 
-static sml_status_t quantize_common(const float* d_in, uint64_t numel, uint32_t P, uint16_t W,
-                                    const int8_t* d_gexp, int32_t* d_payload, int8_t* d_exps_out,
-                                    uint32_t flags, void* stream) {
-    if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
-    if (numel == 0) return SML_OK;
-    if (!d_in || !aligned4(d_in)) return SML_ERR_INVALID_ARG;
-    if (d_payload && !aligned16(d_payload)) return SML_ERR_ALIGNMENT;
-    QuantArgs a;
-    const uint32_t U = quant_slices(P);
-    a.xcd = xcd_chunk_for(U);
-    a.in = d_in;
-    a.numel = numel;
-    a.nblocks = sml_num_blocks(numel, P);
-    const uint64_t te = 256ull * U;
-    a.ntiles = (a.nblocks * P + te - 1) / te;
-    a.gexp = d_gexp;
-    a.payload = reinterpret_cast<u4*>(d_payload);
-    a.exps_out = d_gexp ? nullptr : d_exps_out;
-    a.W = W;
-    dim3 grid(grid_for_tiles(a.ntiles));
-    hipStream_t st = (hipStream_t)stream;
-    const bool al = aligned16(d_in), be = !(flags & SML_FLAG_PAYLOAD_LE), rne = flags & SML_FLAG_ROUND_RNE;
-    // payload store policy by plane size
-    const bool nts = d_payload && nt_from(4 * numel);
-    // Flags outermost, the store policy innermost: the order in which the
-    // instances are created.  hipcc's code for twelve K3 instances (P = 128 /
-    // 256, one slice) differs with it — registers and block layout, same
-    // arithmetic — and this order gives the code that was measured.
-    dispatch_bools([&](auto GLOBAL, auto AL, auto BE, auto RNE) {
-        dispatch_packet(P, [&](auto Pc) {
-            dispatch_slices<1, 2, 4>(U, [&](auto Uc) {
-                dispatch_bools([&](auto NTS) {
-                    // a tile holds whole packets: fewer than P / 256 slices cannot
-                    // occur (quant_slices) and would run 4
-                    constexpr int kUc = Uc() * 256 >= Pc() ? Uc() : 4;
-                    k_quantize_pack<Pc(), AL(), GLOBAL(), BE(), RNE(), kUc, NTS()><<<grid, kBlockThreads, 0, st>>>(a);
-                }, nts);
-            });
-        });
-    }, d_gexp != nullptr, al, be, rne);
-    return launch_check();
-}
-
 sml_status_t sml_exponents(const float* d_in, uint64_t numel, uint32_t packet_numel,
                            int8_t* d_exps, void* stream) {
     if (numel && !d_exps) return SML_ERR_INVALID_ARG;
-    return quantize_common(d_in, numel, packet_numel, 1, nullptr, nullptr, d_exps, 0, stream);
+    return quantize_f32(d_in, numel, packet_numel, 1, nullptr, nullptr, d_exps, 0, stream);
 }
 
 sml_status_t sml_quantize_pack(const float* d_in, uint64_t numel, uint32_t packet_numel,
@@ -577,80 +255,27 @@ sml_status_t sml_quantize_pack(const float* d_in, uint64_t numel, uint32_t packe
     if (num_workers == 0) return SML_ERR_INVALID_ARG;
     if (numel && !d_payload) return SML_ERR_INVALID_ARG;
     if (d_global_exps && d_exps_out && d_exps_out != d_global_exps) return SML_ERR_INVALID_ARG;
-    return quantize_common(d_in, numel, packet_numel, num_workers, d_global_exps, d_payload,
-                           d_exps_out, flags, stream);
+    return quantize_f32(d_in, numel, packet_numel, num_workers, d_global_exps, d_payload, d_exps_out, flags, stream);
 }
 
 sml_status_t sml_dequantize(const int32_t* d_payload, const int8_t* d_exps, uint64_t numel,
                             uint32_t packet_numel, uint16_t num_workers, float* d_out,
                             uint32_t flags, void* stream) {
-    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
-    if (num_workers == 0) return SML_ERR_INVALID_ARG;
-    if (numel == 0) return SML_OK;
-    if (!d_payload || !d_exps || !d_out || !aligned4(d_out)) return SML_ERR_INVALID_ARG;
-    if (!aligned16(d_payload)) return SML_ERR_ALIGNMENT;
-    DequantArgs a;
-    const uint32_t U = stream_slices(2);   // measured: 2-slice tiles +0.6 / +2.8 / +3.3 % at 128 / 256 / 512 MiB
-    a.xcd = xcd_chunk_for(U);
-    a.payload = reinterpret_cast<const u4*>(d_payload);
-    a.exps = d_exps;
-    a.out = d_out;
-    a.numel = numel;
-    a.ntiles = (numel + 256 * U - 1) / (256 * U);
-    a.W = num_workers;
-    dim3 grid(grid_for_tiles(a.ntiles));
-    hipStream_t st = (hipStream_t)stream;
-    const bool al = aligned16(d_out), be = !(flags & SML_FLAG_PAYLOAD_LE);
-    const bool rcp = (a.W & (a.W - 1)) == 0;   // power-of-two W: exact reciprocal
-    const bool nt = nt_from(4 * numel);        // output plane past the Infinity Cache
-    dispatch_packet(packet_numel, [&](auto Pc) {
-        dispatch_slices<2, 4>(U, [&](auto Uc) {
-            dispatch_bools([&](auto AL, auto BE, auto RCP, auto NT) {
-                k_dequantize<Pc(), AL(), BE(), RCP(), NT(), Uc()><<<grid, kBlockThreads, 0, st>>>(a);
-            }, al, be, rcp, nt);
-        });
-    });
-    return launch_check();
+    // measured: 2-slice tiles +0.6 / +2.8 / +3.3 % at 128 / 256 / 512 MiB
+    return plane_dequantize<ElemF32, 2, 4>(d_payload, d_exps, numel, packet_numel, num_workers, d_out,
+                                           aligned16(d_out), stream_slices(2), flags, stream);
 }
 
 sml_status_t sml_roundtrip_loopback(const float* d_in, float* d_out, uint64_t numel,
                                     uint32_t packet_numel, uint16_t num_workers,
                                     int32_t* d_payload, int8_t* d_exps_out,
                                     uint32_t flags, void* stream) {
-    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
-    if (num_workers == 0) return SML_ERR_INVALID_ARG;
-    if (numel == 0) return SML_OK;
-    if (!d_in || !d_out || !aligned4(d_in) || !aligned4(d_out)) return SML_ERR_INVALID_ARG;
-    if (d_payload && !aligned16(d_payload)) return SML_ERR_ALIGNMENT;
-    RoundTripArgs a;
     // a tile holds whole packets: P = 1024 needs 4 slices
     const uint32_t U = packet_numel > 512 ? 4u : stream_slices(2);
-    a.xcd = xcd_chunk_for(U);
-    a.in = d_in;
-    a.out = d_out;
-    a.numel = numel;
-    a.nblocks = sml_num_blocks(numel, packet_numel);
-    a.ntiles = (a.nblocks * packet_numel + 256 * U - 1) / (256 * U);
-    a.payload = reinterpret_cast<u4*>(d_payload);
-    a.exps_out = d_exps_out;
-    a.W = num_workers;
-    dim3 grid(grid_for_tiles(a.ntiles));
-    hipStream_t st = (hipStream_t)stream;
     // in and out share the slice offset, so one alignment test covers both
     // unless the caller passed differently aligned buffers.
-    const bool al = aligned16(d_in) && aligned16(d_out);
-    const bool be = !(flags & SML_FLAG_PAYLOAD_LE), rne = flags & SML_FLAG_ROUND_RNE;
-    const bool nt = nt_from(4 * numel);   // output plane past the Infinity Cache
-    dispatch_packet(packet_numel, [&](auto Pc) {
-        dispatch_slices<2, 4>(U, [&](auto Uc) {
-            dispatch_bools([&](auto AL, auto BE, auto RNE, auto NT) {
-                // P = 1024 always runs 4 slices (U above): a tile holds the packet
-                constexpr int kUc = Pc() == 1024 ? 4 : Uc();
-                k_roundtrip<Pc(), AL(), BE(), RNE(), NT(), kUc><<<grid, kBlockThreads, 0, st>>>(a);
-            }, al, be, rne, nt);
-        });
-    });
-    return launch_check();
+    return plane_roundtrip<ElemF32, 2, 4>(d_in, d_out, aligned16(d_in) && aligned16(d_out), U, numel, packet_numel,
+                                          num_workers, d_payload, d_exps_out, flags, stream);
 }
 
 sml_status_t sml_roundtrip_loopback_batch(const sml_slice* slices, uint32_t num_slices, uint32_t packet_numel,

@@ -143,12 +143,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_switch_aggregate(SwitchArgs a
                 if (a.out && idx < a.numel) {
                     const float s = lut[(uint8_t)e[u]];
                     const u4 q = acc[u];
-                    f4 o;
-                    if constexpr (RCP)
-                        o = mkf4((float)(int32_t)q.x * s, (float)(int32_t)q.y * s, (float)(int32_t)q.z * s,
-                                 (float)(int32_t)q.w * s);
-                    else
-                        o = mkf4(dequantize1(q.x, s), dequantize1(q.y, s), dequantize1(q.z, s), dequantize1(q.w, s));
+                    const f4 o = dequant_words<false, RCP>(q, s);
                     if constexpr (H == 0) {
                         float* out = static_cast<float*>(a.out);
                         if (idx + 4 <= a.numel) store4<ALIGNED>(out + idx, o);

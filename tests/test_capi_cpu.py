@@ -71,6 +71,31 @@ def test_argument_validation_without_gpu(sw):
     assert L.sml_quantize_pack(buf, 16, 256, 1, None, ctypes.c_void_p(addr), None, 0, None) == sw.SML_ERR_ALIGNMENT
     # loopback count must cover whole 16-byte vectors
     assert L.sml_loopback_aggregate(pay, 6, 2, 0, None) == sw.SML_ERR_ALIGNMENT
+    # two checks fail at once: the earlier one decides
+    vp = ctypes.c_void_p
+    b, p16, bad = ctypes.addressof(buf), ctypes.addressof(pay), ctypes.addressof(pay) + 4
+    exps = ctypes.addressof(pay) + 2048
+    # bad packet size with num_workers == 0: sml_quantize_pack looks at num_workers first
+    assert L.sml_quantize_pack(vp(b), 16, 100, 0, None, vp(p16), None, 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_dequantize(vp(p16), vp(exps), 16, 100, 0, vp(b), 0, None) == sw.SML_ERR_UNSUPPORTED
+    assert L.sml_roundtrip_loopback(vp(b), vp(b), 16, 100, 0, None, None, 0, None) == sw.SML_ERR_UNSUPPORTED
+    # null buffer with a misaligned payload plane
+    assert L.sml_quantize_pack(None, 16, 256, 1, None, vp(bad), None, 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_dequantize(vp(bad), vp(exps), 16, 256, 1, None, 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_roundtrip_loopback(None, vp(b), 16, 256, 1, vp(bad), None, 0, None) == sw.SML_ERR_INVALID_ARG
+    # fp32 buffer off its 4-byte alignment with a misaligned payload plane
+    assert L.sml_exponents(vp(b + 2), 16, 256, vp(exps), None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_quantize_pack(vp(b + 2), 16, 256, 1, None, vp(bad), None, 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_dequantize(vp(bad), vp(exps), 16, 256, 1, vp(b + 2), 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_roundtrip_loopback(vp(b + 2), vp(b + 2), 16, 256, 1, vp(bad), None, 0, None) == sw.SML_ERR_INVALID_ARG
+    # numel == 0 with null pointers: nothing to do, unless an earlier check fails
+    assert L.sml_exponents(None, 0, 256, None, None) == sw.SML_OK
+    assert L.sml_roundtrip_loopback(None, None, 0, 256, 1, None, None, 0, None) == sw.SML_OK
+    assert L.sml_quantize_pack(None, 0, 256, 0, None, None, None, 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_dequantize(None, None, 0, 256, 0, None, 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_roundtrip_loopback(None, None, 0, 256, 0, None, None, 0, None) == sw.SML_ERR_INVALID_ARG
+    assert L.sml_exponents(None, 0, 100, None, None) == sw.SML_ERR_UNSUPPORTED
+    assert L.sml_quantize_pack(None, 0, 100, 1, None, None, None, 0, None) == sw.SML_ERR_UNSUPPORTED
 
 
 def test_burst_validation_without_gpu(sw):

@@ -83,6 +83,13 @@ def test_typed_validation_without_gpu(sw, name, dt):
     # next check that fails is a later one (the payload's alignment)
     if name != "exponents":
         assert call(buf + 2, dt, n, P, W, pay + 4, exps) == sw.SML_ERR_ALIGNMENT
+    # two checks fail at once: the earlier one decides
+    assert call(buf, dt, n, 100, 0, pay, exps) == sw.SML_ERR_UNSUPPORTED          # bad P before W = 0
+    assert call(None, dt, n, P, W, pay + 4, exps) == sw.SML_ERR_INVALID_ARG       # null buffer before the payload's alignment
+    assert call(buf + 1, dt, n, P, W, pay + 4, exps) == sw.SML_ERR_INVALID_ARG    # odd pointer before the payload's alignment
+    # nothing to do comes after W = 0 (K2 has no W) and before the pointers
+    assert call(None, dt, 0, P, 0, None, None) == (sw.SML_OK if name == "exponents" else sw.SML_ERR_INVALID_ARG)
+    assert call(None, dt, 0, 100, W, None, None) == sw.SML_ERR_UNSUPPORTED
 
 
 def test_client_data_type_sizes_and_wire_geometry():
