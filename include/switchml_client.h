@@ -63,6 +63,12 @@ void sml_job_release(sml_job_t job);
  * [3] job slices processed, [4] packets (LTUs) processed incl. extra batch. */
 int sml_context_stats(uint64_t out[5]);
 
+/* Batched dispatch counters since Start / ResetStats: out[0] batch calls
+ * issued by the batch worker, out[1] job slices those calls carried,
+ * out[2] job slices the batch worker ran slice by slice (run_slice).
+ * All 0 on the threaded path. */
+int sml_context_batch_stats(uint64_t out[3]);
+
 /* Whether the PrePostProcessor a factory key names (config key
  * general.prepostprocessor; PrePostProcessor::CreateInstance,
  * client_lib/src/prepostprocessor.cc:32-41) accepts per-LTU calls

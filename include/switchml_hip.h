@@ -200,8 +200,10 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
  * Typed buffers of a 16-bit type need 2-byte alignment only (a slice starts
  * at any element) and no byte outside [ptr, ptr + 2 * numel) is touched;
  * payload planes 16-byte aligned, as above.  in == out is allowed for the
- * round trip.  The burst, frames, RDMA and batch entry points take no 16-bit
- * type (a burst whose data_type is one returns SML_ERR_UNSUPPORTED). */
+ * round trip.  Batches of 16-bit slices go through
+ * sml_roundtrip_loopback_batch_typed (below); the burst, frames and RDMA
+ * entry points and sml_roundtrip_loopback_batch take no 16-bit type (a burst
+ * whose data_type is one returns SML_ERR_UNSUPPORTED). */
 sml_status_t sml_exponents_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
                                  uint32_t packet_numel, int8_t* d_exps, void* stream);
 sml_status_t sml_quantize_pack_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
@@ -219,6 +221,44 @@ sml_status_t sml_switch_aggregate_typed(const int32_t* const* d_payloads, const 
                                         uint16_t num_workers, uint64_t numel, uint32_t packet_numel,
                                         int32_t* d_payload_out, int8_t* d_exps_out, void* d_out,
                                         sml_data_type_t data_type, uint32_t flags, void* stream);
+
+/* The batched round trip over slices of any float type (what the client's
+ * batch worker sends: the FIFO slices of the FLOAT32, FLOAT16 and BFLOAT16
+ * jobs queued so far).  Slice i gets exactly
+ *   sml_roundtrip_loopback_typed(in, out, data_type, numel, packet_numel,
+ *                                num_workers, NULL, NULL,
+ *                                flags & SML_FLAG_ROUND_RNE, stream)
+ * — its blocks start at its own first element, no planes are written.  Types
+ * may be mixed in one call; at most SML_MAX_BATCH_SLICES slices over all
+ * types; slices must not overlap each other (a slice's in == out is fine);
+ * numel == 0 slices are skipped.  A 16-bit slice starts at any 2-byte
+ * offset, an fp32 slice at any 4-byte offset, and no byte outside a slice is
+ * read or written.
+ *   Launches: at most one per element type present.  The FLOAT32 slices go
+ * through sml_roundtrip_loopback_batch's kernel, each 16-bit type through its
+ * own instance of the 16-bit batch kernel; a type with one non-empty slice
+ * takes the single-slice kernel.  The order of these launches on `stream` is
+ * unspecified — the slices do not overlap, so it cannot be observed.  Stores
+ * are non-temporal when the call's total output (all slices, all types)
+ * reaches sml_set_payload_nt_threshold.
+ *   Every slice is checked before anything is launched, so a call that
+ * returns one of these has launched nothing: SML_ERR_UNSUPPORTED for a bad
+ * packet_numel, a slice whose data_type is SML_INT32 or any other value, or
+ * more than 2^32 - 1 tiles in one launch; SML_ERR_INVALID_ARG for
+ * num_workers == 0, num_slices > SML_MAX_BATCH_SLICES, slices == NULL with
+ * num_slices > 0, a NULL in / out with numel > 0, a 16-bit slice not 2-byte
+ * aligned, a FLOAT32 slice not 4-byte aligned, or reserved != 0.  A call
+ * without a non-empty slice returns SML_OK and does not touch the device. */
+typedef struct sml_typed_slice {
+    const void* in;
+    void* out;
+    uint64_t numel;
+    uint32_t data_type;   /* sml_data_type_t: SML_FLOAT32, SML_FLOAT16 or SML_BFLOAT16 */
+    uint32_t reserved;    /* 0 */
+} sml_typed_slice;
+sml_status_t sml_roundtrip_loopback_batch_typed(const sml_typed_slice* slices, uint32_t num_slices,
+                                                uint32_t packet_numel, uint16_t num_workers,
+                                                uint32_t flags, void* stream);
 
 /* The switch's exponent half alone (p4/exponents.p4:48-54): d_exps_out[k] =
  * max_w (int8) d_exps[w][k], k < num_blocks — W planes of num_blocks bytes
@@ -524,8 +564,10 @@ uint32_t sml_set_stream_tile_slices(uint32_t slices);
 /* Tuning knob: output planes of at least `bytes` bytes are written with
  * non-temporal stores — the payload plane of sml_quantize_pack (K1/K3), the
  * fp32 output of sml_dequantize (K4), sml_roundtrip_loopback and
- * sml_roundtrip_loopback_batch (by the batch's total output), the fp32
- * output of sml_dequantize_frames, the payloads of a device-memory frame set
+ * sml_roundtrip_loopback_batch (by the batch's total output), the typed
+ * output of their sml_*_typed counterparts (by its bytes;
+ * sml_roundtrip_loopback_batch_typed by the call's total output over every
+ * slice and type), the fp32 output of sml_dequantize_frames, the payloads of a device-memory frame set
  * of sml_quantize_pack_frames (host frame sets keep default stores) and the
  * sml_stream_copy probe; default 64 MiB, a quarter of the 256 MiB Infinity
  * Cache — DESIGN.md §4); UINT64_MAX = never, 0 = always.

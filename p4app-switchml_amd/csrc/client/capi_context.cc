@@ -113,6 +113,15 @@ int sml_context_stats(uint64_t out[5]) {
     return SML_CTX_OK;
 }
 
+int sml_context_batch_stats(uint64_t out[3]) {
+    if (!out) return SML_CTX_ERR_ARG;
+    Stats& s = Context::GetInstance().GetStats();
+    out[0] = s.batch_calls();
+    out[1] = s.batch_slices();
+    out[2] = s.single_slices();
+    return SML_CTX_OK;
+}
+
 int sml_ppp_per_ltu_calls(const char* name) {
     if (!name) return SML_CTX_ERR_ARG;
     const int r = PrePostProcessor::PerLtuCalls(name);

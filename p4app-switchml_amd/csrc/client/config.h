@@ -61,9 +61,9 @@ struct HipBackendConfig {
     bool burst_server = false;
     // mode = fused, loopback switch, no simulated wire: ONE worker thread
     // takes every slice of up to batch_jobs queued jobs (at most
-    // SML_MAX_BATCH_SLICES slices) and runs them in one kernel launch
-    // (sml_roundtrip_loopback_batch) — same FIFO slice geometry and results,
-    // one launch instead of num_worker_threads per job.  0: every worker
+    // SML_MAX_BATCH_SLICES slices) and runs them in one call, one kernel
+    // launch per float type (sml_roundtrip_loopback_batch_typed) — same FIFO
+    // slice geometry and results, instead of num_worker_threads launches per job.  0: every worker
     // thread launches its own slice (the reference's threading).
     uint32_t batch_jobs = 16;
     // Batched dispatch with a zero-copy (pinned host) job in the round: jobs

@@ -21,6 +21,7 @@ void Stats::ResetStats() {
     jobs_submitted_ = 0;
     jobs_finished_ = 0;
     numel_submitted_ = 0;
+    batch_calls_ = batch_slices_ = single_slices_ = 0;
     for (int i = 0; i < n_; i++) slices_[i] = ltus_[i] = bytes_[i] = 0;
 }
 

@@ -28,6 +28,13 @@ class Stats {
     void IncJobsSubmitted(Numel numel) { jobs_submitted_++; numel_submitted_ += numel; }
     void IncJobsFinished() { jobs_finished_++; }
     void AddSlice(WorkerTid tid, uint64_t ltus, uint64_t bytes);
+    // Batched dispatch (LoopbackBackend::BatchMain): one batch call carrying
+    // `slices` job slices; one job slice the batch worker ran through run_slice.
+    void AddBatchCall(uint64_t slices) { batch_calls_++; batch_slices_ += slices; }
+    void AddSingleSlice() { single_slices_++; }
+    uint64_t batch_calls() const { return batch_calls_; }
+    uint64_t batch_slices() const { return batch_slices_; }
+    uint64_t single_slices() const { return single_slices_; }
     uint64_t jobs_submitted() const { return jobs_submitted_; }
     uint64_t jobs_finished() const { return jobs_finished_; }
     uint64_t numel_submitted() const { return numel_submitted_; }
@@ -38,6 +45,7 @@ class Stats {
 
   private:
     std::atomic<uint64_t> jobs_submitted_{0}, jobs_finished_{0}, numel_submitted_{0};
+    std::atomic<uint64_t> batch_calls_{0}, batch_slices_{0}, single_slices_{0};
     std::unique_ptr<std::atomic<uint64_t>[]> slices_, ltus_, bytes_;
     int n_ = 0;
 };

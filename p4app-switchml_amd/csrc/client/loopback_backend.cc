@@ -322,9 +322,10 @@ bool LoopbackBackend::BatchEligible() const {
 // of every job (dummy_worker_thread.cc:73-177) because a CPU core is the unit
 // of parallelism; on the GPU one launch already fills the chip, so here ONE
 // thread takes the queued jobs whole and runs every slice of up to
-// batch_jobs of them in one sml_roundtrip_loopback_batch launch — the same
-// slice geometry (so the same bits) with one launch and one event per batch
-// instead of num_worker_threads per job.  Jobs whose buffers overlap an
+// batch_jobs of them in one sml_roundtrip_loopback_batch_typed call — the
+// same slice geometry (so the same bits) with one launch per element type
+// present (FLOAT32, FLOAT16, BFLOAT16) and one event per batch instead of
+// num_worker_threads launches per job.  Jobs whose buffers overlap an
 // earlier job of the batch start a new launch (stream order keeps them in
 // FIFO order); INT32 and pageable-host jobs run slice by slice through
 // run_slice on the same stream.  Completion of every slice is reported under
@@ -423,17 +424,19 @@ void LoopbackBackend::BatchMain() {
         // buffer shared with an earlier job of the batch: stream order keeps
         // FIFO order) do not pay an event between kernels each.
         Batch cur;
-        std::vector<sml_slice> segs;
+        std::vector<sml_typed_slice> segs;
         size_t seg_first = 0;                                   // first piece of the pending launch
         std::vector<std::pair<uintptr_t, uintptr_t>> reads, writes;   // kernel address ranges of the pending launch
-        // Launch the pending slices (one sml_roundtrip_loopback_batch); a
-        // failure fails exactly those slices.
+        // Launch the pending slices (one sml_roundtrip_loopback_batch_typed:
+        // fp32, fp16 and bf16 slices in one table); a failure fails exactly
+        // those slices.
         auto launch = [&]() {
             if (!segs.empty()) {
+                context_.GetStats().AddBatchCall(segs.size());
                 try {
-                    sml_ok(sml_roundtrip_loopback_batch(segs.data(), (uint32_t)segs.size(), (uint32_t)P,
-                                                        g.num_workers, rne, hip_ppp->stream()),
-                           "sml_roundtrip_loopback_batch");
+                    sml_ok(sml_roundtrip_loopback_batch_typed(segs.data(), (uint32_t)segs.size(), (uint32_t)P,
+                                                              g.num_workers, rne, hip_ppp->stream()),
+                           "sml_roundtrip_loopback_batch_typed");
                 } catch (const std::exception& e) {
                     fprintf(stderr, "[switchml] batch worker: %s\n", e.what());
                     (void)hipStreamSynchronize(hip_ppp->stream());
@@ -456,7 +459,8 @@ void LoopbackBackend::BatchMain() {
             const bool work = t.numel > 0 && !g.instant_job_completion && hip_ppp;
             void* in_d = work ? DeviceAddress(t.in_ptr) : nullptr;
             void* out_d = work ? DeviceAddress(t.out_ptr) : nullptr;
-            const bool batched = work && t.data_type == FLOAT32 && in_d && out_d;
+            const bool is_float = t.data_type == FLOAT32 || IsHalfType(t.data_type);
+            const bool batched = work && is_float && in_d && out_d;
             if (batched) {
                 const uintptr_t i0 = (uintptr_t)in_d, i1 = i0 + t.numel * esz;
                 const uintptr_t o0 = (uintptr_t)out_d, o1 = o0 + t.numel * esz;
@@ -481,8 +485,10 @@ void LoopbackBackend::BatchMain() {
                 } else if (batched) {
                     const uint64_t B = n / P + (n % P != 0);
                     pc.packets = B + std::min<uint64_t>(B, bmax);
-                    segs.push_back(sml_slice{static_cast<const float*>(in_d) + off, static_cast<float*>(out_d) + off, n});
+                    segs.push_back(sml_typed_slice{static_cast<const char*>(in_d) + off * esz,
+                                                   static_cast<char*>(out_d) + off * esz, n, (uint32_t)t.data_type, 0u});
                 } else {
+                    context_.GetStats().AddSingleSlice();
                     try {
                         pc.packets = run_slice(*ppp, config_, ws, pc.js, nullptr, (WorkerTid)tid);
                     } catch (const std::exception& e) {

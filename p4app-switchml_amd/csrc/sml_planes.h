@@ -274,6 +274,55 @@ __global__ __launch_bounds__(kBlockThreads) void k_roundtrip(RoundTripArgs<typen
     }
 }
 
+// The fused round trip over a batch of slices (of one or several jobs) in ONE
+// launch: the slices' tiles are numbered consecutively (tile_end[s] = tiles of
+// slices 0..s), each wave finds its slice by a binary search over that
+// wave-uniform table (kernel arguments, scalar loads) and runs the slice's
+// own block geometry.  Slices start at any element (FIFO slices, pinned host
+// tensors): fp32 takes the unaligned form, which streams at the aligned rate,
+// a 16-bit type its one form.  1808 bytes of kernel arguments for every T.
+template <class T>
+struct RoundTripBatchArgs {
+    const T* in[SML_MAX_BATCH_SLICES];
+    T* out[SML_MAX_BATCH_SLICES];
+    uint64_t numel[SML_MAX_BATCH_SLICES];
+    uint32_t tile_end[SML_MAX_BATCH_SLICES];
+    uint32_t nslices;
+    uint32_t W;
+    uint32_t xcd;
+};
+static_assert(sizeof(RoundTripBatchArgs<float>) <= 4096 && sizeof(RoundTripBatchArgs<uint16_t>) == sizeof(RoundTripBatchArgs<float>),
+              "the table travels as kernel arguments");
+
+template <int P, class E, bool RNE, bool NT = false, int U = kU>
+__global__ __launch_bounds__(kBlockThreads) void k_roundtrip_batch(RoundTripBatchArgs<typename E::raw> a) {
+    __shared__ float lut[256];
+    build_lut(lut, a.W);
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t nwaves = gridDim.x * kWavesPerBlock;
+    const uint32_t ntiles = a.tile_end[a.nslices - 1];
+    for (uint32_t t = (uint32_t)xcd_block(a.xcd) * kWavesPerBlock + wave_index(); t < ntiles; t += nwaves) {
+        uint32_t lo = 0, hi = a.nslices - 1;             // first s with tile_end[s] > t
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.tile_end[mid] > t) hi = mid;
+            else lo = mid + 1;
+        }
+        const uint32_t t0 = lo ? a.tile_end[lo - 1] : 0u;
+        RoundTripArgs<typename E::raw> r;
+        r.in = a.in[lo];
+        r.out = a.out[lo];
+        r.numel = a.numel[lo];
+        r.nblocks = r.numel / P + (r.numel % P != 0);
+        r.ntiles = a.tile_end[lo] - t0;
+        r.payload = nullptr;
+        r.exps_out = nullptr;
+        r.W = a.W;
+        r.xcd = a.xcd;
+        roundtrip_tile<P, E, true, RNE, NT, U>(r, t - t0, lut, lane);
+    }
+}
+
 // ------------------------------------------------------------ host side
 //
 // One set-up per kernel, for every element type: EV<V> is the element policy
@@ -390,6 +439,35 @@ sml_status_t plane_roundtrip(const T* d_in, T* d_out, bool variant, uint32_t U, 
     });
     return launch_check();
 }
+
+// One slice into the table of a batched launch on tiles of `tile` elements
+// (a table holds at most SML_MAX_BATCH_SLICES: the callers' check).  Empty
+// slices touch nothing and take no entry.
+template <class T>
+sml_status_t batch_add(RoundTripBatchArgs<T>& a, uint64_t& tiles, const void* in, void* out, uint64_t numel, uint32_t P,
+                       uint64_t tile) {
+    if (numel == 0) return SML_OK;
+    const T* i = static_cast<const T*>(in);
+    T* o = static_cast<T*>(out);
+    if (!i || !o || !elem_aligned(i) || !elem_aligned(o)) return SML_ERR_INVALID_ARG;
+    tiles += (sml_num_blocks(numel, P) * P + tile - 1) / tile;
+    if (tiles > 0xFFFFFFFFull) return SML_ERR_UNSUPPORTED;
+    a.in[a.nslices] = i;
+    a.out[a.nslices] = o;
+    a.numel[a.nslices] = numel;
+    a.tile_end[a.nslices] = (uint32_t)tiles;
+    a.nslices++;
+    return SML_OK;
+}
+
+// The fp32 batched launch (sml_quantizer.hip) in its two steps, for
+// sml_roundtrip_loopback_batch_typed (sml_half.hip), which fills and checks
+// the tables of every type before it launches any: the elements of an fp32
+// batch tile for packets of P, and the launch of a filled table (one slice:
+// the single-slice kernel) with non-temporal stores or not.
+uint64_t batch_tile_f32(uint32_t P);
+sml_status_t batch_launch_f32(RoundTripBatchArgs<float>& a, uint32_t P, uint16_t W, uint32_t flags, bool nt,
+                              void* stream);
 
 }  // namespace sml
 

@@ -18,51 +18,6 @@ std::atomic<uint32_t> g_xcd_chunk{64};
 
 // -------------------------------------------------------------- kernels
 
-// The fused round trip over a batch of slices (of one or several jobs) in ONE
-// launch: the slices' tiles are numbered consecutively (tile_end[s] = tiles of
-// slices 0..s), each wave finds its slice by a binary search over that
-// wave-uniform table (kernel arguments, scalar loads) and runs the slice's
-// own block geometry.  Slices start at any 4-byte offset (FIFO slices,
-// pinned host tensors): the unaligned form, which streams at the aligned rate.
-struct RoundTripBatchArgs {
-    const float* in[SML_MAX_BATCH_SLICES];
-    float* out[SML_MAX_BATCH_SLICES];
-    uint64_t numel[SML_MAX_BATCH_SLICES];
-    uint32_t tile_end[SML_MAX_BATCH_SLICES];
-    uint32_t nslices;
-    uint32_t W;
-    uint32_t xcd;
-};
-
-template <int P, bool RNE, bool NT = false, int U = kU>
-__global__ __launch_bounds__(kBlockThreads) void k_roundtrip_batch(RoundTripBatchArgs a) {
-    __shared__ float lut[256];
-    build_lut(lut, a.W);
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t nwaves = gridDim.x * kWavesPerBlock;
-    const uint32_t ntiles = a.tile_end[a.nslices - 1];
-    for (uint32_t t = (uint32_t)xcd_block(a.xcd) * kWavesPerBlock + wave_index(); t < ntiles; t += nwaves) {
-        uint32_t lo = 0, hi = a.nslices - 1;             // first s with tile_end[s] > t
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (a.tile_end[mid] > t) hi = mid;
-            else lo = mid + 1;
-        }
-        const uint32_t t0 = lo ? a.tile_end[lo - 1] : 0u;
-        RoundTripArgs<float> r;
-        r.in = a.in[lo];
-        r.out = a.out[lo];
-        r.numel = a.numel[lo];
-        r.nblocks = r.numel / P + (r.numel % P != 0);
-        r.ntiles = a.tile_end[lo] - t0;
-        r.payload = nullptr;
-        r.exps_out = nullptr;
-        r.W = a.W;
-        r.xcd = a.xcd;
-        roundtrip_tile<P, ElemF32<false>, true, RNE, NT, U>(r, t - t0, lut, lane);
-    }
-}
-
 // Word streams in the quantizer's tile shape (1024 words per wave, 16-B
 // non-temporal loads, default-policy stores, XCD order, one-shot grid; any
 // 4-byte alignment; in may alias out):
@@ -181,6 +136,38 @@ static sml_status_t quantize_f32(const float* d_in, uint64_t numel, uint32_t P, 
                                             d_exps_out, flags, stream);
 }
 
+// Tile slices of the fp32 batch (P = 1024: 4): the single-slice round trip's
+// 2 — against 4 on 4 cold jobs: a 256 MiB job as 4 FIFO slices 86.22 ->
+// 85.86 us, 4 x 25 MiB buckets 36.10 -> 35.32 us
+// (profiles/r04/ab_batch_slices.json).
+static uint32_t batch_slices_f32(uint32_t P) { return P > 512 ? 4u : 2u; }
+
+uint64_t batch_tile_f32(uint32_t P) { return (uint64_t)batch_slices_f32(P) * kWave * 4; }
+
+sml_status_t batch_launch_f32(RoundTripBatchArgs<float>& a, uint32_t P, uint16_t W, uint32_t flags, bool nt,
+                              void* stream) {
+    if (a.nslices == 0) return SML_OK;
+    if (a.nslices == 1)   // one slice: the single-slice kernel (aligned form when the slice allows it)
+        return sml_roundtrip_loopback(a.in[0], a.out[0], a.numel[0], P, W, nullptr, nullptr,
+                                      flags & SML_FLAG_ROUND_RNE, stream);
+    const uint32_t U = batch_slices_f32(P);
+    a.xcd = xcd_chunk_for(U);
+    a.W = W;
+    const dim3 grid(grid_for_tiles(a.tile_end[a.nslices - 1]));
+    hipStream_t st = (hipStream_t)stream;
+    const bool rne = flags & SML_FLAG_ROUND_RNE;
+    dispatch_packet(P, [&](auto Pc) {
+        dispatch_slices<2, kU>(U, [&](auto Uc) {
+            dispatch_bools([&](auto RNE, auto NT) {
+                // P = 1024 always runs the default slices (U above): a tile holds the packet
+                constexpr int kUc = Pc() <= 512 ? Uc() : kU;
+                k_roundtrip_batch<Pc(), ElemF32<false>, RNE(), NT(), kUc><<<grid, kBlockThreads, 0, st>>>(a);
+            }, rne, nt);
+        });
+    });
+    return launch_check();
+}
+
 }  // namespace sml
 
 using namespace sml;
@@ -282,48 +269,17 @@ sml_status_t sml_roundtrip_loopback_batch(const sml_slice* slices, uint32_t num_
                                           uint16_t num_workers, uint32_t flags, void* stream) {
     if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (num_workers == 0 || num_slices > SML_MAX_BATCH_SLICES || (num_slices && !slices)) return SML_ERR_INVALID_ARG;
-    RoundTripBatchArgs a;
-    // tile slices (P = 1024: 4): the single-slice round trip's 2 — against 4
-    // on 4 cold jobs: a 256 MiB job as 4 FIFO slices 86.22 -> 85.86 us, 4 x
-    // 25 MiB buckets 36.10 -> 35.32 us (profiles/r04/ab_batch_slices.json).
-    const uint32_t U = packet_numel > 512 ? 4u : 2u;
-    const uint64_t tile = (uint64_t)U * kWave * 4;
-    a.xcd = xcd_chunk_for(U);
-    a.W = num_workers;
+    RoundTripBatchArgs<float> a;
     a.nslices = 0;
-    uint64_t tiles = 0;
+    uint64_t tiles = 0, out_bytes = 0;
     for (uint32_t i = 0; i < num_slices; i++) {
-        const sml_slice& sl = slices[i];
-        if (sl.numel == 0) continue;                      // empty slices touch nothing
-        if (!sl.in || !sl.out || !aligned4(sl.in) || !aligned4(sl.out)) return SML_ERR_INVALID_ARG;
-        tiles += (sml_num_blocks(sl.numel, packet_numel) * packet_numel + tile - 1) / tile;
-        if (tiles > 0xFFFFFFFFull) return SML_ERR_UNSUPPORTED;
-        a.in[a.nslices] = sl.in;
-        a.out[a.nslices] = sl.out;
-        a.numel[a.nslices] = sl.numel;
-        a.tile_end[a.nslices] = (uint32_t)tiles;
-        a.nslices++;
+        const sml_status_t s = batch_add(a, tiles, slices[i].in, slices[i].out, slices[i].numel, packet_numel,
+                                         batch_tile_f32(packet_numel));
+        if (s != SML_OK) return s;
+        out_bytes += 4 * slices[i].numel;
     }
-    if (a.nslices == 0) return SML_OK;
-    if (a.nslices == 1)   // one slice: the single-slice kernel (aligned form when the slice allows it)
-        return sml_roundtrip_loopback(a.in[0], a.out[0], a.numel[0], packet_numel, num_workers, nullptr, nullptr,
-                                      flags & SML_FLAG_ROUND_RNE, stream);
-    const dim3 grid(grid_for_tiles(tiles));
-    hipStream_t st = (hipStream_t)stream;
     // the outputs of the whole batch past the Infinity Cache: non-temporal stores
-    uint64_t out_bytes = 0;
-    for (uint32_t i = 0; i < a.nslices; i++) out_bytes += 4 * a.numel[i];
-    const bool rne = flags & SML_FLAG_ROUND_RNE, nt = nt_from(out_bytes);
-    dispatch_packet(packet_numel, [&](auto Pc) {
-        dispatch_slices<2, kU>(U, [&](auto Uc) {
-            dispatch_bools([&](auto RNE, auto NT) {
-                // P = 1024 always runs the default slices (U above): a tile holds the packet
-                constexpr int kUc = Pc() <= 512 ? Uc() : kU;
-                k_roundtrip_batch<Pc(), RNE(), NT(), kUc><<<grid, kBlockThreads, 0, st>>>(a);
-            }, rne, nt);
-        });
-    });
-    return launch_check();
+    return batch_launch_f32(a, packet_numel, num_workers, flags, nt_from(out_bytes), stream);
 }
 
 sml_status_t sml_rdma_imm(const int8_t* d_exps, uint64_t B, uint32_t batch_max, uint32_t* d_imm, void* stream) {

@@ -162,6 +162,8 @@ def lib():
     L.sml_dequantize_typed.argtypes = [vp, vp, u64, u32, u16, vp, i32, u32, vp]
     L.sml_roundtrip_loopback_typed.restype = i32
     L.sml_roundtrip_loopback_typed.argtypes = [vp, vp, i32, u64, u32, u16, vp, vp, u32, vp]
+    L.sml_roundtrip_loopback_batch_typed.restype = i32
+    L.sml_roundtrip_loopback_batch_typed.argtypes = [vp, u32, u32, u16, u32, vp]
     L.sml_switch_aggregate_typed.restype = i32
     L.sml_switch_aggregate_typed.argtypes = [vp, vp, u16, u64, u32, vp, vp, vp, i32, u32, vp]
     L.sml_copy_segments.restype = i32
@@ -457,19 +459,38 @@ class Slice(ctypes.Structure):
 MAX_BATCH_SLICES = 64
 
 
+class TypedSlice(ctypes.Structure):
+    """sml_typed_slice: one job slice of a batched round trip over any float type."""
+    _fields_ = [("in_", ctypes.c_void_p), ("out", ctypes.c_void_p), ("numel", ctypes.c_uint64),
+                ("data_type", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 def roundtrip_loopback_batch(slices, packet_numel: int = 256, num_workers: int = 1, flags: int = 0, stream=None):
-    """The fused round trip over several slices in one launch
-    (sml_roundtrip_loopback_batch): `slices` is a list of (x, out) fp32
-    device (or pinned host) tensors; slice i gets exactly
+    """The fused round trip over several slices in one call: `slices` is a
+    list of (x, out) device (or pinned host) tensor pairs, fp32, fp16 or bf16
+    (a pair's two dtypes equal, the pairs' dtypes free); slice i gets exactly
     roundtrip_loopback(x_i, out=out_i) — its blocks start at its own first
-    element."""
+    element.  An all-fp32 list is one sml_roundtrip_loopback_batch launch; a
+    list with a 16-bit slice goes whole through
+    sml_roundtrip_loopback_batch_typed (one launch per dtype present)."""
     torch = _torch()
-    arr = (Slice * max(1, len(slices)))()
-    for i, (x, o) in enumerate(slices):
+    for x, o in slices:
         if x.numel() != o.numel():
             raise ValueError("slice in/out sizes differ")
-        arr[i] = Slice(_dev(x, torch.float32, "x").value, _dev(o, torch.float32, "out").value, x.numel())
+        if getattr(x, "dtype", None) != getattr(o, "dtype", None):
+            raise TypeError(f"slice in/out dtypes differ: {x.dtype}, {o.dtype}")
     st = _stream(stream, slices[0][0]) if slices else None
+    if any(getattr(x, "dtype", None) in (torch.float16, torch.bfloat16) for x, _ in slices):
+        tarr = (TypedSlice * len(slices))()
+        for i, (x, o) in enumerate(slices):
+            dt = _float_type(x.dtype, "x")
+            tarr[i] = TypedSlice(_dev(x, x.dtype, "x").value, _dev(o, x.dtype, "out").value, x.numel(), dt, 0)
+        _check("sml_roundtrip_loopback_batch_typed", lib().sml_roundtrip_loopback_batch_typed(
+            tarr, len(slices), packet_numel, num_workers, flags, st))
+        return
+    arr = (Slice * max(1, len(slices)))()
+    for i, (x, o) in enumerate(slices):
+        arr[i] = Slice(_dev(x, torch.float32, "x").value, _dev(o, torch.float32, "out").value, x.numel())
     _check("sml_roundtrip_loopback_batch", lib().sml_roundtrip_loopback_batch(
         arr, len(slices), packet_numel, num_workers, flags, st))
 

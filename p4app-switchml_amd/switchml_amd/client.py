@@ -43,6 +43,8 @@ def _lib():
         L.sml_job_release.argtypes = [vp]
         L.sml_context_stats.restype = i32
         L.sml_context_stats.argtypes = [vp]
+        L.sml_context_batch_stats.restype = i32
+        L.sml_context_batch_stats.argtypes = [vp]
         L.sml_ppp_per_ltu_calls.restype = i32
         L.sml_ppp_per_ltu_calls.argtypes = [ctypes.c_char_p]
         _bound = True
@@ -181,6 +183,15 @@ def stats() -> dict:
     arr = (ctypes.c_uint64 * 5)()
     _ok(_lib().sml_context_stats(ctypes.cast(arr, ctypes.c_void_p)), "sml_context_stats")
     return dict(zip(("jobs_submitted", "jobs_finished", "numel_submitted", "slices", "packets"), list(arr)))
+
+
+def batch_stats() -> dict:
+    """Batched dispatch counters (sml_context_batch_stats): batch calls the
+    batch worker issued, the job slices they carried, and the job slices it
+    ran one by one; all 0 on the threaded path."""
+    arr = (ctypes.c_uint64 * 3)()
+    _ok(_lib().sml_context_batch_stats(ctypes.cast(arr, ctypes.c_void_p)), "sml_context_batch_stats")
+    return dict(zip(("launches", "batched_slices", "single_slices"), list(arr)))
 
 
 def ppp_per_ltu_calls(name: str) -> bool:
