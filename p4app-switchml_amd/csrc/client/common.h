@@ -4,7 +4,7 @@
 // job.h:36-70 (reference paths relative to /root/reference/dev_root/) so code
 // written against the reference compiles unchanged against this header.
 // Tensor pointers may be HOST or DEVICE memory: the loopback backend detects
-// which (hipPointerGetAttributes) and stages host tensors through HBM.
+// which (QueryPointer, hip_util.h) and stages host tensors through HBM.
 #ifndef SWITCHML_AMD_COMMON_H_
 #define SWITCHML_AMD_COMMON_H_
 
@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <thread>
 
 namespace switchml {
 
@@ -87,6 +88,20 @@ inline Numel WireBytes(const Tensor& t) {
 // stream, an idle worker waiting for the next job), in microseconds.
 // SWITCHML_SPIN_US overrides the default; 0 = always sleep at once.
 int SpinMicros();
+
+// The poll before every sleep: call done() until it holds or SpinMicros() has
+// passed (once at least), yielding the CPU between polls if asked to.  Returns
+// whether it held; what a waiter does when it did not (block on the stream or
+// event, sleep on a condition variable) is the caller's.
+template <class Pred>
+bool SpinUntil(Pred done, bool yield_between = false) {
+    const auto until = clock::now() + std::chrono::microseconds(SpinMicros());
+    do {
+        if (done()) return true;
+        if (yield_between) std::this_thread::yield();
+    } while (clock::now() < until);
+    return false;
+}
 
 }  // namespace switchml
 

@@ -1,9 +1,6 @@
 // fifo_scheduler.cc — see fifo_scheduler.h.
 #include "fifo_scheduler.h"
 
-#include <chrono>
-#include <thread>
-
 namespace switchml {
 
 bool Barrier::Wait() {
@@ -22,10 +19,10 @@ bool Barrier::Wait() {
         // other: poll for a short while before sleeping (a futex wake-up per
         // job costs about as much as a 25 MiB bucket's kernels).
         lock.unlock();
-        const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(SpinMicros());
-        while (generation_flag_.load(std::memory_order_acquire) == gen &&
-               !destroyed_flag_.load(std::memory_order_acquire) && std::chrono::steady_clock::now() < until)
-            std::this_thread::yield();
+        SpinUntil([&] {
+            return generation_flag_.load(std::memory_order_acquire) != gen ||
+                   destroyed_flag_.load(std::memory_order_acquire);
+        }, true);
         lock.lock();
     }
     cv_.wait(lock, [&] { return generation_ != gen || destroyed_; });
@@ -85,10 +82,9 @@ bool FifoScheduler::GetJobSlice(WorkerTid tid, JobSlice& job_slice) {
         // for a short while before sleeping, so the next job does not pay a
         // futex wake-up.
         lock.unlock();
-        const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(SpinMicros());
-        while (!stopped_flag_.load(std::memory_order_acquire) && queue_size_.load(std::memory_order_acquire) == 0 &&
-               std::chrono::steady_clock::now() < until)
-            std::this_thread::yield();
+        SpinUntil([this] {
+            return stopped_flag_.load(std::memory_order_acquire) || queue_size_.load(std::memory_order_acquire) != 0;
+        }, true);
         lock.lock();
     }
     job_submitted_event_.wait(lock, [this] { return stopped_ || !queue_.empty(); });
@@ -116,10 +112,9 @@ bool FifoScheduler::GetJobs(size_t max_jobs, std::vector<std::shared_ptr<Job>>& 
     std::unique_lock<std::mutex> lock(access_mutex_);
     if (!stopped_ && queue_.empty() && SpinMicros() > 0) {
         lock.unlock();
-        const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(SpinMicros());
-        while (!stopped_flag_.load(std::memory_order_acquire) && queue_size_.load(std::memory_order_acquire) == 0 &&
-               std::chrono::steady_clock::now() < until)
-            std::this_thread::yield();
+        SpinUntil([this] {
+            return stopped_flag_.load(std::memory_order_acquire) || queue_size_.load(std::memory_order_acquire) != 0;
+        }, true);
         lock.lock();
     }
     job_submitted_event_.wait(lock, [this] { return stopped_ || !queue_.empty(); });

@@ -1,18 +1,10 @@
 // hip_exponent_quantizer_ppp.cc — see hip_exponent_quantizer_ppp.h.
 #include "hip_exponent_quantizer_ppp.h"
 
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
 #include <string>
 
-#include "switchml_hip.h"
-
 namespace switchml {
-
-static void hip_ok(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw SwitchMLFatal(std::string(what) + ": " + hipGetErrorString(e));
-}
 
 HipExponentQuantizerPPP::HipExponentQuantizerPPP(Config& config, WorkerTid worker_tid, Numel ltu_size,
                                                  Numel batch_num_ltus, bool per_ltu_calls)
@@ -107,29 +99,6 @@ void HipExponentQuantizerPPP::ensure_single_buffers() {
     }
 }
 
-namespace {
-
-// Where a packet buffer lives, and the address a kernel can use for it:
-// device memory and pinned (page-locked, device-mapped) host memory are
-// written / read by the kernels directly; pageable host memory is staged.
-struct PacketMem {
-    void* dev = nullptr;   // kernel-usable address, null for pageable memory
-    bool host = true;      // the CPU may touch it right after the call returns
-};
-
-PacketMem packet_mem(void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return {};
-    }
-    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) return {p, false};
-    if (a.type == hipMemoryTypeHost && a.devicePointer) return {a.devicePointer, true};
-    return {};
-}
-
-}  // namespace
-
 // PreprocessSingle — ppp.cc:69-192.  One kernel per half (quantize of block
 // ltu_id - b, exponent of block ltu_id), writing the packet buffer directly
 // when the device can address it.  The packet is complete on return, as the
@@ -156,8 +125,8 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
         if (ltu_id >= batch_num_ltus_) {
             const uint64_t k = ltu_id - batch_num_ltus_;
             const uint64_t off = k * P, n = std::min<uint64_t>(P, s.numel - off);
-            const PacketMem m = packet_mem(entries_ptr);
-            sync |= m.host;
+            const PointerInfo m = QueryPointer(entries_ptr);
+            sync |= m.host();
             // the kernel writes all P words of the block; the reference writes
             // only the n real ones (ppp.cc:102-109), so a partial block is staged
             int32_t* dst = (m.dev && n == P) ? static_cast<int32_t*>(m.dev) : d_stage_;
@@ -170,8 +139,8 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
         }
         if (ltu_id < total_main_num_ltus_) {
             const uint64_t off = ltu_id * P, n = std::min<uint64_t>(P, s.numel - off);
-            const PacketMem m = packet_mem(extra_info);
-            sync |= m.host;
+            const PointerInfo m = QueryPointer(extra_info);
+            sync |= m.host();
             // one byte: the int8 exponent in byte 0 of the extra-info slot (byte 1 untouched)
             int8_t* dst = m.dev ? static_cast<int8_t*>(m.dev) : d_stage_exp_;
             check(sml_exponents(static_cast<const float*>(s.in_ptr) + off, n, P, dst, stream_), "sml_exponents");
@@ -180,8 +149,8 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
         }
     } else if (s.data_type == INT32) {
         const uint64_t off = ltu_id * P, n = std::min<uint64_t>(P, s.numel - off);
-        const PacketMem m = packet_mem(entries_ptr);
-        sync |= m.host;
+        const PointerInfo m = QueryPointer(entries_ptr);
+        sync |= m.host();
         int32_t* dst = m.dev ? static_cast<int32_t*>(m.dev) : d_stage_;
         check(sml_bswap_i32(static_cast<const int32_t*>(s.in_ptr) + off, dst, n, stream_), "sml_bswap_i32");
         if (dst == d_stage_)
@@ -206,8 +175,8 @@ void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_
         if (ltu_id >= batch_num_ltus_) {
             const uint64_t k = ltu_id - batch_num_ltus_;
             const uint64_t off = k * P, n = std::min<uint64_t>(P, s.numel - off);
-            const PacketMem m = packet_mem(entries_ptr);
-            sync |= m.host;
+            const PointerInfo m = QueryPointer(entries_ptr);
+            sync |= m.host();
             const int32_t* src = static_cast<const int32_t*>(m.dev);
             if (!src) {
                 hip_ok(hipMemcpyAsync(d_stage_, entries_ptr, n * 4, hipMemcpyDefault, stream_), "hipMemcpyAsync");
@@ -221,14 +190,14 @@ void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_
         if (ltu_id < total_main_num_ltus_) {
             // ppp.cc:254-260 stores the scale of the received exponent; the
             // kernels derive the same scale from the stored exponent.
-            sync |= packet_mem(extra_info).host;
+            sync |= QueryPointer(extra_info).host();
             hip_ok(hipMemcpyAsync(d_recv_exps_ + ltu_id, extra_info, 1, hipMemcpyDefault, stream_),
                    "hipMemcpyAsync");
         }
     } else if (s.data_type == INT32) {
         const uint64_t off = ltu_id * P, n = std::min<uint64_t>(P, s.numel - off);
-        const PacketMem m = packet_mem(entries_ptr);
-        sync |= m.host;
+        const PointerInfo m = QueryPointer(entries_ptr);
+        sync |= m.host();
         const int32_t* src = static_cast<const int32_t*>(m.dev);
         if (!src) {
             hip_ok(hipMemcpyAsync(d_stage_, entries_ptr, n * 4, hipMemcpyDefault, stream_), "hipMemcpyAsync");
@@ -261,22 +230,18 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
     // one pool per slice: the query is cached for the slice (SetupJobSlice resets it)
     if (entries[0] != pool_probe_) {
         pool_probe_ = entries[0];
-        const PacketMem pm = packet_mem(entries[0]);
-        pool_dev_ = pm.dev;
-        pool_host_ = pm.host;
+        pool_ = QueryPointer(entries[0]);
     }
-    const PacketMem m{pool_dev_, pool_host_};
+    const PointerInfo m = pool_;
     // the extra-info slots may be another allocation (a separate ring, a
     // second registration): queried on their own
-    PacketMem xm{};
+    PointerInfo xm;
     if (extras && extras[0]) {
         if (extras[0] != xpool_probe_) {
             xpool_probe_ = extras[0];
-            const PacketMem pm = packet_mem(extras[0]);
-            xpool_dev_ = pm.dev;
-            xpool_host_ = pm.host;
+            xpool_ = QueryPointer(extras[0]);
         }
-        xm = {xpool_dev_, xpool_host_};
+        xm = xpool_;
     }
     if (!m.dev || (extras && extras[0] && !xm.dev)) {
         if (kind == BurstKind::kProcessExchange)
@@ -302,7 +267,7 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
         if (!p || !per_buffer) return p;
         auto it = dev_of_.find(p);   // a NIC pool's buffers recur burst after burst: one query per slice
         if (it != dev_of_.end()) return it->second;
-        void* a = packet_mem(p).dev;
+        void* a = QueryPointer(p).dev;
         if (!a) throw SwitchMLFatal("burst: a packet buffer of the burst is not device-addressable");
         dev_of_.emplace(p, a);
         return a;
@@ -321,7 +286,7 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
     b.flags = (kind == BurstKind::kProcessExchange ? SML_FLAG_PROCESS_PACKET : 0u) | round_flags_;
     const char* what = kind == BurstKind::kPre ? "sml_preprocess_burst"
                        : kind == BurstKind::kPost ? "sml_postprocess_burst" : "sml_exchange_burst";
-    const bool serve = m.host && config_.backend_.hip.burst_server;
+    const bool serve = m.host() && config_.backend_.hip.burst_server;
     if (serve && !server_) {
         check(sml_burst_server_create((uint32_t)ltu_numel_, round_flags_, 100, &server_), "sml_burst_server_create");
     }
@@ -347,7 +312,7 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
               what);
     }
     if (serve) return;
-    if (m.host || !stream_ordered_) hip_ok(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    if (m.host() || !stream_ordered_) hip_ok(hipStreamSynchronize(stream_), "hipStreamSynchronize");
 }
 
 void HipExponentQuantizerPPP::PreprocessBurst(uint32_t n, const uint64_t* ltu_ids, void* const* entries,

@@ -15,12 +15,10 @@
 #ifndef SWITCHML_AMD_HIP_EXPONENT_QUANTIZER_PPP_H_
 #define SWITCHML_AMD_HIP_EXPONENT_QUANTIZER_PPP_H_
 
-#include <hip/hip_runtime_api.h>
-
 #include <unordered_map>
 
+#include "hip_util.h"
 #include "prepostprocessor.h"
-#include "switchml_hip.h"
 
 namespace switchml {
 
@@ -107,14 +105,12 @@ class HipExponentQuantizerPPP : public PrePostProcessor {
     // rounding), else 0: or'ed into every quantizing launch
     uint32_t round_flags_ = 0;
     // where the slice's packet pool lives (burst calls): the first buffer
-    // pointer seen, and its packet_mem() answer — for the entries and, as a
+    // pointer seen, and QueryPointer's answer — for the entries and, as a
     // separate query, the extra-info slots (they may be another allocation)
     void* pool_probe_ = nullptr;
-    void* pool_dev_ = nullptr;
-    bool pool_host_ = true;
+    PointerInfo pool_;
     void* xpool_probe_ = nullptr;
-    void* xpool_dev_ = nullptr;
-    bool xpool_host_ = true;
+    PointerInfo xpool_;
     // host -> device address of each packet buffer of the slice, when the
     // pool's addresses differ (a hipHostRegister'd pool): queried per buffer
     std::unordered_map<void*, void*> dev_of_;

@@ -1,9 +1,7 @@
 // job.cc — Job lifecycle (client_lib/src/job.cc).
 #include "job.h"
 
-#include <chrono>
 #include <cstdlib>
-#include <thread>
 
 namespace switchml {
 
@@ -25,17 +23,13 @@ Job::Job(Tensor tensor, JobType job_type, ExtraJobInfo extra_job_info)
 void Job::WaitToComplete() {
     // GPU jobs finish in tens of microseconds: poll briefly before sleeping on
     // the condition variable (a futex wake-up costs about as much as the job).
-    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(SpinMicros());
-    do {
+    const auto done = [this] {
         const JobStatus s = job_status_.load(std::memory_order_acquire);
-        if (s == FINISHED || s == FAILED) return;
-        std::this_thread::yield();
-    } while (std::chrono::steady_clock::now() < until);
-    std::unique_lock<std::mutex> lock(access_mutex_);
-    job_finished_event_.wait(lock, [this] {
-        JobStatus s = job_status_.load();
         return s == FINISHED || s == FAILED;
-    });
+    };
+    if (SpinUntil(done, true)) return;
+    std::unique_lock<std::mutex> lock(access_mutex_);
+    job_finished_event_.wait(lock, done);
 }
 
 void Job::SetJobStatus(JobStatus status) {

@@ -1,48 +1,37 @@
 // loopback_backend.cc — see loopback_backend.h.
 #include "loopback_backend.h"
 
-#include <hip/hip_runtime_api.h>
-#include <time.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <vector>
 #include <cstdio>
 #include <memory>
 #include <string>
 
+#include "batch_plan.h"
 #include "context.h"
 #include "hip_exponent_quantizer_ppp.h"
+#include "hip_util.h"
 #include "prepostprocessor.h"
-#include "switchml_hip.h"
 #include "xgmi_switch.h"
 
 namespace switchml {
 
 namespace {
 
-void hip_ok(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw SwitchMLFatal(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-void sml_ok(int s, const char* what) {
-    if (s != SML_OK)
-        throw SwitchMLFatal(std::string(what) + ": " + sml_status_string((sml_status_t)s) + " " + sml_last_error());
-}
-
 // Wait for the worker's stream: poll for a short while (a slice's kernels
 // usually finish within it), then block in hipStreamSynchronize.
 void stream_wait(hipStream_t st) {
-    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(SpinMicros());
-    do {
+    const bool done = SpinUntil([st] {
         const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) hip_ok(q, "hipStreamQuery");
-    } while (std::chrono::steady_clock::now() < until);
-    hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (q != hipSuccess && q != hipErrorNotReady) hip_ok(q, "hipStreamQuery");
+        return q == hipSuccess;
+    });
+    if (!done) hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
 }
 
 // Grow-only device buffer owned by one worker thread, used only on that
@@ -189,11 +178,11 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
     // their device mapping (the kernels read and write them over PCIe, both
     // directions at once — "zero-copy"); pageable host tensors are
     // staged through HBM with copies on the worker's stream.
-    void* in_d = DeviceAddress(t.in_ptr);
+    const PointerInfo in = QueryPointer(t.in_ptr);
     // the in-node switch reads its input twice (exponents, then quantize):
     // a host input is copied into HBM once instead of crossing PCIe twice
-    if (xs && in_d && !IsDevicePointer(t.in_ptr)) in_d = nullptr;
-    void* out_d = DeviceAddress(t.out_ptr);
+    void* in_d = (xs && !in.device) ? nullptr : in.dev;
+    void* out_d = QueryPointer(t.out_ptr).dev;
 
     JobSlice staged = js;
     if (in_d) {
@@ -241,61 +230,193 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
 // Wait for an event: poll for a short while (a slice's kernels usually finish
 // within it), then block.
 void event_wait(hipEvent_t ev) {
-    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(SpinMicros());
-    do {
+    const bool done = SpinUntil([ev] {
         const hipError_t q = hipEventQuery(ev);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) hip_ok(q, "hipEventQuery");
-    } while (std::chrono::steady_clock::now() < until);
-    hip_ok(hipEventSynchronize(ev), "hipEventSynchronize");
+        if (q != hipSuccess && q != hipErrorNotReady) hip_ok(q, "hipEventQuery");
+        return q == hipSuccess;
+    });
+    if (!done) hip_ok(hipEventSynchronize(ev), "hipEventSynchronize");
 }
 
-// The oldest in-flight slice's event, while no later job is queued yet: poll
+// The oldest in-flight entry's event, while no later job is queued yet: poll
 // for either its completion or a new job (a framework posts its buckets one
 // call at a time — blocking on the event would serialize the next job behind
 // this one's kernels), for SpinMicros(); then block on the event.  True: the
-// event completed (or failed: the caller's retire reports it); false: a job
+// event completed (or failed: retiring it reports that); false: a job
 // arrived first, go and overlap it.
 template <class HasJob>
 bool event_or_job(hipEvent_t ev, HasJob has_job) {
-    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(SpinMicros());
-    do {
-        if (hipEventQuery(ev) != hipErrorNotReady) return true;
-        if (has_job()) return false;
-    } while (std::chrono::steady_clock::now() < until);
+    bool job = false;
+    SpinUntil([&] { return hipEventQuery(ev) != hipErrorNotReady || (job = has_job()); });
+    return !job;
+}
+
+// The work of one worker whose kernels are still running on its stream, oldest
+// first: each entry is a payload and the event recorded after its work.  The
+// worker takes the next job while the GPU finishes the previous one, and every
+// entry is published, in order, once its event has passed.  At most
+// kMaxInFlight entries; the events are pooled and destroyed with the queue.
+constexpr size_t kMaxInFlight = 4;
+
+template <class Payload>
+class InFlightQueue {
+  public:
+    // publish(payload, error): error is null when the entry's event completed,
+    // else what waiting for it threw
+    typedef std::function<void(Payload&, const char* error)> Publish;
+    explicit InFlightQueue(Publish publish) : publish_(std::move(publish)) {}
+    ~InFlightQueue() {
+        for (hipEvent_t ev : pool_) (void)hipEventDestroy(ev);
+    }
+
+    // Record an event after the work queued on `st` so far and enter the
+    // payload under it.  Throws, with the payload left to the caller, if HIP
+    // refuses.
+    void Push(hipStream_t st, Payload&& payload) {
+        if (pool_.empty()) {
+            hipEvent_t ev;
+            hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+            pool_.push_back(ev);
+        }
+        hip_ok(hipEventRecord(pool_.back(), st), "hipEventRecord");
+        entries_.push_back(Entry{pool_.back(), std::move(payload)});
+        pool_.pop_back();
+    }
+
+    // Wait for the oldest entry and publish it.
+    void RetireOldest() {
+        Entry& e = entries_.front();
+        std::string error;
+        try {
+            event_wait(e.ev);
+        } catch (const std::exception& ex) {
+            error = ex.what();
+        }
+        publish_(e.payload, error.empty() ? nullptr : error.c_str());
+        pool_.push_back(e.ev);
+        entries_.pop_front();
+    }
+
+    // A worker's first step of every round.  Retires every entry whose event
+    // is no longer pending; then, if the queue is full or no job follows
+    // (job_follows() is false), there is nothing to overlap with and the
+    // oldest entry is finished first — unless poll_for_job is set and a job
+    // arrives while it is waited for.  True: start the round again.
+    template <class HasJob>
+    bool Settle(HasJob job_follows, bool poll_for_job) {
+        while (!entries_.empty() && hipEventQuery(entries_.front().ev) != hipErrorNotReady) RetireOldest();
+        if (entries_.empty() || (entries_.size() < kMaxInFlight && job_follows())) return false;
+        if (entries_.size() >= kMaxInFlight || !poll_for_job || event_or_job(entries_.front().ev, job_follows))
+            RetireOldest();
+        return true;
+    }
+
+    // Stopping, or a stream in doubt: the entries own their buffers until
+    // their kernels finish.
+    void Drain() {
+        while (!entries_.empty()) RetireOldest();
+    }
+
+  private:
+    struct Entry {
+        hipEvent_t ev;
+        Payload payload;
+    };
+    Publish publish_;
+    std::deque<Entry> entries_;
+    std::vector<hipEvent_t> pool_;
+};
+
+// One round of the batch worker: the jobs it took whole, where their tensors
+// live (one query per pointer) and, once planned, their T pieces each.
+struct Round {
+    std::vector<std::shared_ptr<Job>> jobs;
+    std::vector<PlanJob> where;   // the planner's view of each job
+    bool host_input = false;      // a job reads pinned host memory (zero-copy)
+    std::vector<PlanPiece> pieces;
+};
+
+JobSlice SliceOf(const Round& r, const PlanPiece& pc) {
+    JobSlice js{r.jobs[pc.job], r.jobs[pc.job]->tensor_};
+    js.slice.numel = pc.numel;
+    js.slice.OffsetPtrs(pc.offset);
+    return js;
+}
+
+// Take the queued jobs, up to max_jobs in the round (blocks while the round is
+// empty and nothing is queued); false when the context stopped instead.
+bool TakeJobs(Context& ctx, size_t max_jobs, Round& r, uint64_t& last_seq) {
+    if (!ctx.GetJobs(max_jobs, r.jobs)) return false;
+    last_seq = r.jobs.back()->sched_seq.load(std::memory_order_relaxed);
+    for (size_t j = r.where.size(); j < r.jobs.size(); j++) {
+        const Tensor& t = r.jobs[j]->tensor_;
+        const PointerInfo in = t.numel > 0 ? QueryPointer(t.in_ptr) : PointerInfo();
+        const PointerInfo out = t.numel > 0 ? QueryPointer(t.out_ptr) : PointerInfo();
+        r.where.push_back(PlanJob{in.dev, out.dev, t.numel, t.data_type});
+        r.host_input = r.host_input || in.host_mapped();
+    }
     return true;
+}
+
+// Zero-copy host buckets: a framework posts its buckets one call at a time, so
+// the first one would otherwise go alone into a small launch; PCIe moves
+// 31 GB/s each way in a 26 MB launch but 37-42 in 100 MB+ ones
+// (profiles/r02/zero_copy_probes.json).  While the next job follows within
+// coalesce_us of the last, it joins this round.
+void CoalesceHostBuckets(Context& ctx, uint32_t coalesce_us, size_t max_jobs, Round& r, uint64_t& last_seq) {
+    if (coalesce_us == 0 || !r.host_input) return;
+    auto last = std::chrono::steady_clock::now();
+    while (r.jobs.size() < max_jobs && ctx.GetContextState() == Context::RUNNING) {
+        if (ctx.HasJobAfter(last_seq)) {
+            if (!TakeJobs(ctx, max_jobs, r, last_seq)) break;
+            last = std::chrono::steady_clock::now();
+        } else if (std::chrono::steady_clock::now() - last > std::chrono::microseconds(coalesce_us)) {
+            break;
+        } else {
+            std::this_thread::yield();
+        }
+    }
+}
+
+// Queue the plan's steps on the pre/post-processor's stream, in order.  A step
+// that fails fails exactly its own pieces, after the stream has drained:
+// nothing may still touch their buffers when they are published FAILED.
+void ExecutePlan(const BatchPlan& plan, Round& r, Context& ctx, const Config& cfg, HipExponentQuantizerPPP& ppp,
+                 WorkerState& ws) {
+    const uint32_t rne = cfg.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u;   // the VCL=1 build's rounding
+    std::vector<sml_typed_slice> table;
+    for (const PlanStep& s : plan.steps) {
+        try {
+            if (s.kind == PlanStep::kLaunch) {   // fp32, fp16 and bf16 slices in one table
+                table.clear();
+                for (size_t i = s.first; i < s.first + s.count; i++) {
+                    const PlanSlice& sl = plan.slices[i];
+                    table.push_back(sml_typed_slice{sl.in, sl.out, sl.numel, (uint32_t)sl.data_type, 0u});
+                }
+                ctx.GetStats().AddBatchCall(table.size());
+                sml_ok(sml_roundtrip_loopback_batch_typed(table.data(), (uint32_t)table.size(),
+                                                          (uint32_t)cfg.general_.packet_numel,
+                                                          cfg.general_.num_workers, rne, ppp.stream()),
+                       "sml_roundtrip_loopback_batch_typed");
+            } else {   // INT32 and pageable-host slices
+                PlanPiece& pc = r.pieces[s.first];
+                JobSlice js = SliceOf(r, pc);
+                ctx.GetStats().AddSingleSlice();
+                pc.packets = run_slice(ppp, cfg, ws, js, nullptr, pc.tid);
+            }
+        } catch (const std::exception& e) {
+            fprintf(stderr, "[switchml] batch worker: job %llu failed: %s\n",
+                    (unsigned long long)r.jobs[r.pieces[s.fail_first].job]->id_, e.what());
+            (void)hipStreamSynchronize(ppp.stream());
+            for (size_t i = s.fail_first; i < s.fail_end; i++) r.pieces[i].ok = false;
+        }
+    }
 }
 
 }  // namespace
 
-void* DeviceAddress(void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) return p;
-    if (a.type == hipMemoryTypeHost && a.devicePointer) return a.devicePointer;
-    return nullptr;
-}
-
-bool IsHostMapped(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeHost && a.devicePointer;
-}
-
-bool IsDevicePointer(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
+void* DeviceAddress(void* p) { return QueryPointer(p).dev; }
+bool IsDevicePointer(const void* p) { return QueryPointer(p).device; }
 
 LoopbackBackend::LoopbackBackend(Context& context, Config& config) : context_(context), config_(config) {}
 
@@ -331,6 +452,8 @@ bool LoopbackBackend::BatchEligible() const {
 // run_slice on the same stream.  Completion of every slice is reported under
 // its own worker thread id, so the scheduler, Stats and failure semantics are
 // those of the threaded path.
+// What shares a launch, what splits one and what a failure fails is decided
+// by PlanBatch (batch_plan.h); the rounds in flight are an InFlightQueue.
 void LoopbackBackend::BatchMain() {
     const GeneralConfig& g = config_.general_;
     const int T = g.num_worker_threads;
@@ -342,189 +465,49 @@ void LoopbackBackend::BatchMain() {
         fprintf(stderr, "[switchml] batch worker: %s\n", e.what());
     }
     auto* hip_ppp = dynamic_cast<HipExponentQuantizerPPP*>(ppp.get());
-    const uint64_t P = g.packet_numel;
-    const uint64_t bmax = g.max_outstanding_packets / T;
     const size_t max_jobs = std::max<size_t>(1, std::min<size_t>(config_.backend_.hip.batch_jobs,
                                                                   SML_MAX_BATCH_SLICES / std::max(1, T)));
-    const uint32_t coalesce_us = config_.backend_.hip.coalesce_us;
-    const uint32_t rne = config_.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u;   // the VCL=1 build's rounding
-    struct Piece {
-        JobSlice js;
-        WorkerTid tid;
-        uint64_t packets;
-        bool ok;
-    };
-    struct Batch {
-        std::vector<Piece> pieces;
-        hipEvent_t ev = nullptr;
-    };
-    constexpr size_t kMaxInFlight = 4;
-    std::deque<Batch> inflight;
-    std::vector<hipEvent_t> events;
-    auto publish = [&](std::vector<Piece>& pieces, bool ok) {
-        for (Piece& pc : pieces) {
-            const bool good = ok && pc.ok;
-            if (good) context_.GetStats().AddSlice(pc.tid, pc.packets, pc.js.slice.numel * DataTypeSize(pc.js.slice.data_type));
-            context_.NotifyJobSliceCompletion(pc.tid, pc.js, good);
+    const PlanParams params{T, g.packet_numel, g.max_outstanding_packets / T, config_.backend_.dummy.fail_worker_thread,
+                            g.instant_job_completion, hip_ppp != nullptr, SML_MAX_BATCH_SLICES};
+    auto publish = [this](Round& r, const char* error) {
+        if (error) fprintf(stderr, "[switchml] batch worker: %s\n", error);
+        for (const PlanPiece& pc : r.pieces) {
+            const JobSlice js = SliceOf(r, pc);
+            const bool good = !error && pc.ok;
+            if (good) context_.GetStats().AddSlice(pc.tid, pc.packets, pc.numel * DataTypeSize(js.slice.data_type));
+            context_.NotifyJobSliceCompletion(pc.tid, js, good);
         }
     };
-    auto retire = [&]() {
-        Batch& b = inflight.front();
-        bool ok = true;
-        try {
-            event_wait(b.ev);
-        } catch (const std::exception& e) {
-            fprintf(stderr, "[switchml] batch worker: %s\n", e.what());
-            ok = false;
-        }
-        publish(b.pieces, ok);
-        events.push_back(b.ev);
-        inflight.pop_front();
-    };
+    InFlightQueue<Round> inflight(publish);
     WorkerState ws;
-    std::vector<std::shared_ptr<Job>> jobs;
     uint64_t last_seq = 0;
     while (context_.GetContextState() == Context::RUNNING) {
-        while (!inflight.empty() && hipEventQuery(inflight.front().ev) != hipErrorNotReady) retire();
-        if (!inflight.empty() && (inflight.size() >= kMaxInFlight || !context_.HasJobAfter(last_seq))) {
-            // nothing to overlap with: finish the oldest batch first.  (Unlike the
-            // threaded path this does not poll for a new job meanwhile: jobs that
-            // arrive while the batch runs join the next launch — for zero-copy
-            // host buckets larger launches move more bytes per second over PCIe;
-            // measured: configs[4] pinned 2.95 ms this way, 3.23 ms polling.)
-            retire();
-            continue;
-        }
-        jobs.clear();
-        if (!context_.GetJobs(max_jobs, jobs)) continue;
-        last_seq = jobs.back()->sched_seq.load(std::memory_order_relaxed);
-        // Zero-copy host buckets: a framework posts its buckets one call at a
-        // time, so the first one would otherwise go alone into a small launch;
-        // PCIe moves 31 GB/s each way in a 26 MB launch but 37-42 in 100 MB+
-        // ones (profiles/r02/zero_copy_probes.json).  While the next job
-        // follows within coalesce_us of the last, it joins this launch.
-        if (coalesce_us > 0 && jobs.size() < max_jobs) {
-            bool host = false;
-            for (const auto& j : jobs) host = host || (j->tensor_.numel > 0 && IsHostMapped(j->tensor_.in_ptr));
-            auto last = std::chrono::steady_clock::now();
-            while (host && jobs.size() < max_jobs && context_.GetContextState() == Context::RUNNING) {
-                if (context_.HasJobAfter(last_seq)) {
-                    if (!context_.GetJobs(max_jobs, jobs)) break;
-                    last_seq = jobs.back()->sched_seq.load(std::memory_order_relaxed);
-                    last = std::chrono::steady_clock::now();
-                    continue;
-                }
-                if (std::chrono::steady_clock::now() - last > std::chrono::microseconds(coalesce_us)) break;
-                std::this_thread::yield();
-            }
-        }
-
+        // Nothing to overlap with: finish the oldest round first.  (Unlike the
+        // threaded path this does not poll for a new job meanwhile: jobs that
+        // arrive while the round runs join the next launch — for zero-copy
+        // host buckets larger launches move more bytes per second over PCIe;
+        // measured: configs[4] pinned 2.95 ms this way, 3.23 ms polling.)
+        if (inflight.Settle([&] { return context_.HasJobAfter(last_seq); }, false)) continue;
+        Round cur;
+        if (!TakeJobs(context_, max_jobs, cur, last_seq)) continue;
+        CoalesceHostBuckets(context_, config_.backend_.hip.coalesce_us, max_jobs, cur, last_seq);
+        BatchPlan plan = PlanBatch(cur.where, params);
+        cur.pieces = std::move(plan.pieces);
+        if (hip_ppp) ExecutePlan(plan, cur, context_, config_, *hip_ppp, ws);
         // Every job taken here shares ONE completion event, recorded after
-        // the last launch: jobs that must be split into several launches (a
-        // buffer shared with an earlier job of the batch: stream order keeps
-        // FIFO order) do not pay an event between kernels each.
-        Batch cur;
-        std::vector<sml_typed_slice> segs;
-        size_t seg_first = 0;                                   // first piece of the pending launch
-        std::vector<std::pair<uintptr_t, uintptr_t>> reads, writes;   // kernel address ranges of the pending launch
-        // Launch the pending slices (one sml_roundtrip_loopback_batch_typed:
-        // fp32, fp16 and bf16 slices in one table); a failure fails exactly
-        // those slices.
-        auto launch = [&]() {
-            if (!segs.empty()) {
-                context_.GetStats().AddBatchCall(segs.size());
-                try {
-                    sml_ok(sml_roundtrip_loopback_batch_typed(segs.data(), (uint32_t)segs.size(), (uint32_t)P,
-                                                              g.num_workers, rne, hip_ppp->stream()),
-                           "sml_roundtrip_loopback_batch_typed");
-                } catch (const std::exception& e) {
-                    fprintf(stderr, "[switchml] batch worker: %s\n", e.what());
-                    (void)hipStreamSynchronize(hip_ppp->stream());
-                    for (size_t i = seg_first; i < cur.pieces.size(); i++) cur.pieces[i].ok = false;
-                }
-            }
-            segs.clear();
-            reads.clear();
-            writes.clear();
-            seg_first = cur.pieces.size();
-        };
-        auto overlaps = [](const std::vector<std::pair<uintptr_t, uintptr_t>>& v, uintptr_t a, uintptr_t b) {
-            for (const auto& r : v)
-                if (a < r.second && r.first < b) return true;
-            return false;
-        };
-        for (auto& job : jobs) {
-            const Tensor& t = job->tensor_;
-            const size_t esz = DataTypeSize(t.data_type);
-            const bool work = t.numel > 0 && !g.instant_job_completion && hip_ppp;
-            void* in_d = work ? DeviceAddress(t.in_ptr) : nullptr;
-            void* out_d = work ? DeviceAddress(t.out_ptr) : nullptr;
-            const bool is_float = t.data_type == FLOAT32 || IsHalfType(t.data_type);
-            const bool batched = work && is_float && in_d && out_d;
-            if (batched) {
-                const uintptr_t i0 = (uintptr_t)in_d, i1 = i0 + t.numel * esz;
-                const uintptr_t o0 = (uintptr_t)out_d, o1 = o0 + t.numel * esz;
-                if (overlaps(writes, i0, i1) || overlaps(writes, o0, o1) || overlaps(reads, o0, o1)) launch();
-                reads.emplace_back(i0, i1);
-                writes.emplace_back(o0, o1);
-            } else if (work) {
-                launch();   // keep FIFO order on the stream
-            }
-            for (int tid = 0; tid < T; tid++) {
-                Piece pc{JobSlice(), (WorkerTid)tid, 0, true};
-                pc.js.job = job;
-                pc.js.slice = t;
-                Numel off, n;
-                FifoSliceGeometry(t.numel, T, tid, &off, &n);
-                pc.js.slice.numel = n;
-                pc.js.slice.OffsetPtrs(off);
-                if (!work || n == 0) {
-                    pc.ok = work || t.numel == 0 || g.instant_job_completion;   // no pre/post-processor: failed
-                } else if (tid == config_.backend_.dummy.fail_worker_thread) {
-                    pc.ok = false;   // injected fault: this slice's buffers are not touched
-                } else if (batched) {
-                    const uint64_t B = n / P + (n % P != 0);
-                    pc.packets = B + std::min<uint64_t>(B, bmax);
-                    segs.push_back(sml_typed_slice{static_cast<const char*>(in_d) + off * esz,
-                                                   static_cast<char*>(out_d) + off * esz, n, (uint32_t)t.data_type, 0u});
-                } else {
-                    context_.GetStats().AddSingleSlice();
-                    try {
-                        pc.packets = run_slice(*ppp, config_, ws, pc.js, nullptr, (WorkerTid)tid);
-                    } catch (const std::exception& e) {
-                        fprintf(stderr, "[switchml] batch worker: job %llu failed: %s\n",
-                                (unsigned long long)job->id_, e.what());
-                        (void)hipStreamSynchronize(hip_ppp->stream());
-                        pc.ok = false;
-                    }
-                }
-                cur.pieces.push_back(std::move(pc));
-            }
-            if (!batched) seg_first = cur.pieces.size();   // its slices are not part of a pending launch
-        }
-        if (hip_ppp) launch();
-        // one event for everything taken in this round
+        // the last launch: jobs that must be split into several launches do
+        // not pay an event between kernels each.
         try {
             if (!hip_ppp) throw SwitchMLFatal("no pre/post-processor");
-            if (events.empty()) {
-                hipEvent_t ev;
-                hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-                events.push_back(ev);
-            }
-            cur.ev = events.back();
-            hip_ok(hipEventRecord(cur.ev, hip_ppp->stream()), "hipEventRecord");
-            events.pop_back();
-            inflight.push_back(std::move(cur));
+            inflight.Push(hip_ppp->stream(), std::move(cur));
         } catch (const std::exception& e) {
-            fprintf(stderr, "[switchml] batch worker: %s\n", e.what());
             if (hip_ppp) (void)hipStreamSynchronize(hip_ppp->stream());   // nothing may still touch the buffers
-            while (!inflight.empty()) retire();
-            publish(cur.pieces, false);
+            inflight.Drain();
+            publish(cur, e.what());
         }
     }
-    // stopping: batches in flight own their buffers until their kernels finish
-    while (!inflight.empty()) retire();
-    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+    // stopping: rounds in flight own their buffers until their kernels finish
+    inflight.Drain();
 }
 
 void LoopbackBackend::CleanupWorker() {
@@ -554,34 +537,21 @@ void LoopbackBackend::WorkerMain(WorkerTid tid) {
     }
     auto* hip_ppp = dynamic_cast<HipExponentQuantizerPPP*>(ppp.get());
     const float bw = config_.backend_.dummy.bandwidth;
-    // Slices whose kernels are still running: the worker takes the next job's
-    // slice (when one is queued) while the GPU finishes the previous one, and
-    // publishes each slice's completion, in order, once its event has passed.
-    // Up to kMaxInFlight per worker; the simulated wire (bandwidth > 0) keeps
-    // the strict one-at-a-time loop of dummy_worker_thread.cc.
-    constexpr size_t kMaxInFlight = 4;
+    // Slices whose kernels are still running (InFlightQueue); the simulated
+    // wire (bandwidth > 0) keeps the strict one-at-a-time loop of
+    // dummy_worker_thread.cc.
     struct InFlight {
         JobSlice js;
-        hipEvent_t ev;
         uint64_t packets;
     };
-    std::deque<InFlight> inflight;
-    std::vector<hipEvent_t> events;
-    auto retire = [&](bool wait) {
-        InFlight& f = inflight.front();
-        bool ok = true;
-        try {
-            if (wait) event_wait(f.ev);
-        } catch (const std::exception& e) {
+    InFlightQueue<InFlight> inflight([this, tid](InFlight& f, const char* error) {
+        if (error)
             fprintf(stderr, "[switchml] worker thread %d: job %llu failed: %s\n", tid,
-                    (unsigned long long)f.js.job->id_, e.what());
-            ok = false;
-        }
-        if (ok) context_.GetStats().AddSlice(tid, f.packets, f.js.slice.numel * DataTypeSize(f.js.slice.data_type));
-        context_.NotifyJobSliceCompletion(tid, f.js, ok);
-        events.push_back(f.ev);
-        inflight.pop_front();
-    };
+                    (unsigned long long)f.js.job->id_, error);
+        else
+            context_.GetStats().AddSlice(tid, f.packets, f.js.slice.numel * DataTypeSize(f.js.slice.data_type));
+        context_.NotifyJobSliceCompletion(tid, f.js, !error);
+    });
     WorkerState ws;
     JobSlice js;
     uint64_t last_seq = 0;  // sched_seq of the last job this thread took a slice of
@@ -590,14 +560,8 @@ void LoopbackBackend::WorkerMain(WorkerTid tid) {
     bool wedged = false;
     const DummyBackendConfig& dummy = config_.backend_.dummy;
     while (context_.GetContextState() == Context::RUNNING) {
-        while (!inflight.empty() && hipEventQuery(inflight.front().ev) != hipErrorNotReady) retire(true);
-        if (!inflight.empty() && (inflight.size() >= kMaxInFlight || !context_.HasJobAfter(last_seq))) {
-            // nothing to overlap with (yet): finish the oldest slice, unless a job arrives first
-            if (inflight.size() >= kMaxInFlight ||
-                event_or_job(inflight.front().ev, [&] { return context_.HasJobAfter(last_seq); }))
-                retire(true);
-            continue;
-        }
+        // nothing to overlap with (yet): finish the oldest slice, unless a job arrives first
+        if (inflight.Settle([&] { return context_.HasJobAfter(last_seq); }, true)) continue;
         if (!context_.GetJobSlice(tid, js)) continue;
         last_seq = js.job->sched_seq.load(std::memory_order_relaxed);
         // empty slices and instant_job_completion never touch the PPP
@@ -618,15 +582,7 @@ void LoopbackBackend::WorkerMain(WorkerTid tid) {
                     sml_ok(sml_debug_stall(dummy.stall_ms * 1000u, hip_ppp->stream()), "sml_debug_stall");
                 packets = run_slice(*ppp, config_, ws, js, xgmi_.get(), tid);
                 if (hip_ppp && bw <= 0) {
-                    if (events.empty()) {
-                        hipEvent_t ev;
-                        hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-                        events.push_back(ev);
-                    }
-                    hipEvent_t ev = events.back();
-                    hip_ok(hipEventRecord(ev, hip_ppp->stream()), "hipEventRecord");
-                    events.pop_back();
-                    inflight.push_back(InFlight{js, ev, packets});
+                    inflight.Push(hip_ppp->stream(), InFlight{js, packets});
                     js = JobSlice();
                     continue;
                 }
@@ -665,8 +621,7 @@ void LoopbackBackend::WorkerMain(WorkerTid tid) {
     }
     // stopping: the in-flight slices still own their buffers until their
     // kernels finish; then they are published (FAILED: the context stopped)
-    while (!inflight.empty()) retire(true);
-    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+    inflight.Drain();
 }
 
 }  // namespace switchml

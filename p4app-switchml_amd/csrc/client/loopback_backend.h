@@ -39,7 +39,10 @@ class LoopbackBackend {
   private:
     void WorkerMain(WorkerTid tid);
     // backend.hip.batch_jobs > 0, mode = fused, loopback switch, no simulated
-    // wire, HIP pre/post-processor: one thread, batched launches (BatchMain).
+    // wire, HIP pre/post-processor: one thread, batched launches (BatchMain:
+    // take jobs, query their pointers, PlanBatch (batch_plan.h), run the
+    // plan's steps, one event per round).  Both loops keep the work whose
+    // kernels still run in an InFlightQueue (loopback_backend.cc).
     bool BatchEligible() const;
     void BatchMain();
 
@@ -51,6 +54,7 @@ class LoopbackBackend {
     std::unique_ptr<XgmiSwitch> xgmi_;   // general.backend = "xgmi": the in-node switch
 };
 
+// Views of QueryPointer (hip_util.h) for callers outside the client.
 // True if p is HIP device (or managed) memory; false for host memory.
 bool IsDevicePointer(const void* p);
 // Address a kernel can use for p: p for device / managed memory, the device

@@ -16,7 +16,7 @@
 #include <cstring>
 #include <thread>
 
-#include "switchml_hip.h"
+#include "hip_util.h"
 
 namespace switchml {
 
@@ -27,15 +27,7 @@ constexpr int kMaxW = SML_MAX_SWITCH_WORKERS;
 constexpr int kMaxT = 16;
 constexpr size_t kHandle = sizeof(hipIpcMemHandle_t);
 
-void hip_ok(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw SwitchMLFatal(std::string("xgmi switch: ") + what + ": " + hipGetErrorString(e));
-}
-
-void sml_ok(int s, const char* what) {
-    if (s != SML_OK)
-        throw SwitchMLFatal(std::string("xgmi switch: ") + what + ": " + sml_status_string((sml_status_t)s) + " " +
-                            sml_last_error());
-}
+constexpr const char* kWho = "xgmi switch: ";   // every hip_ok / sml_ok message here starts with it
 
 // Reapers of wedged switches (XgmiSwitch::Wedged): how many are still
 // waiting for their streams to drain before they free what they hold.
@@ -183,7 +175,7 @@ XgmiSwitch::XgmiSwitch(const Config& config, int device) {
 }
 
 void XgmiSwitch::Setup(int device) {
-    hip_ok(hipSetDevice(device), "hipSetDevice");
+    hip_ok(hipSetDevice(device), "hipSetDevice", kWho);
     device_ = device;
     {
         // an earlier switch of this process that wedged still holds peer
@@ -202,20 +194,20 @@ void XgmiSwitch::Setup(int device) {
     planes_.resize(T_);
     for (int t = 0; t < T_; t++) {
         ThreadPlanes& tp = planes_[t];
-        hip_ok(hipMalloc(&tp.exps, cap_b), "hipMalloc");
+        hip_ok(hipMalloc(&tp.exps, cap_b), "hipMalloc", kWho);
         // + W packets of the largest size: the inbox's W rows of ceil(B / W)
         // blocks may exceed B blocks by up to W - 1 (push form)
-        hip_ok(hipMalloc(&tp.payload, (cap_ + (uint64_t)kMaxW * 1024) * 4), "hipMalloc");
-        hip_ok(hipMalloc(&tp.out, cap_ * 4), "hipMalloc");
-        hip_ok(hipMalloc(&tp.gexp, cap_b), "hipMalloc");
-        hip_ok(hipStreamCreateWithFlags(&tp.xst, hipStreamNonBlocking), "hipStreamCreate");
+        hip_ok(hipMalloc(&tp.payload, (cap_ + (uint64_t)kMaxW * 1024) * 4), "hipMalloc", kWho);
+        hip_ok(hipMalloc(&tp.out, cap_ * 4), "hipMalloc", kWho);
+        hip_ok(hipMalloc(&tp.gexp, cap_b), "hipMalloc", kWho);
+        hip_ok(hipStreamCreateWithFlags(&tp.xst, hipStreamNonBlocking), "hipStreamCreate", kWho);
         ShmPlanes& sp = shm_->planes[rank_][t];
         hipIpcMemHandle_t h;
-        hip_ok(hipIpcGetMemHandle(&h, tp.exps), "hipIpcGetMemHandle");
+        hip_ok(hipIpcGetMemHandle(&h, tp.exps), "hipIpcGetMemHandle", kWho);
         memcpy(sp.exps, &h, kHandle);
-        hip_ok(hipIpcGetMemHandle(&h, tp.payload), "hipIpcGetMemHandle");
+        hip_ok(hipIpcGetMemHandle(&h, tp.payload), "hipIpcGetMemHandle", kWho);
         memcpy(sp.payload, &h, kHandle);
-        hip_ok(hipIpcGetMemHandle(&h, tp.out), "hipIpcGetMemHandle");
+        hip_ok(hipIpcGetMemHandle(&h, tp.out), "hipIpcGetMemHandle", kWho);
         memcpy(sp.out, &h, kHandle);
         sp.published.store(1, std::memory_order_release);
     }
@@ -260,15 +252,15 @@ void XgmiSwitch::OpenPeers() {
             void* p;
             hipIpcMemHandle_t h;
             memcpy(&h, sp.exps, kHandle);
-            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
+            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle", kWho);
             opened_.push_back(p);
             tp.peer_exps[w] = static_cast<const int8_t*>(p);
             memcpy(&h, sp.payload, kHandle);
-            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
+            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle", kWho);
             opened_.push_back(p);
             tp.peer_payload[w] = static_cast<const int32_t*>(p);
             memcpy(&h, sp.out, kHandle);
-            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
+            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle", kWho);
             opened_.push_back(p);
             tp.peer_out[w] = static_cast<const float*>(p);
         }
@@ -404,7 +396,7 @@ bool XgmiSwitch::StreamSync(hipStream_t st, bool bounded_only) {
         if (q != hipErrorNotReady) {
             wedged_.store(true, std::memory_order_release);   // a failed stream: its work's state is unknown
             if (bounded_only) return false;
-            hip_ok(q, "hipStreamQuery");
+            hip_ok(q, "hipStreamQuery", kWho);
         }
         if (spins > 256) {
             std::this_thread::yield();
@@ -420,7 +412,7 @@ bool XgmiSwitch::StreamSync(hipStream_t st, bool bounded_only) {
 namespace {
 // The writer's half of every hand-off to the peers: write
 // this GPU's L2 back before the stream sync that precedes the barrier.
-void release(hipStream_t st) { sml_ok(sml_release_to_peers(st), "sml_release_to_peers"); }
+void release(hipStream_t st) { sml_ok(sml_release_to_peers(st), "sml_release_to_peers", kWho); }
 constexpr uint32_t kPeer = SML_FLAG_PEER_PLANES;   // the reader's half: acquire in the reading kernels
 }  // namespace
 
@@ -430,10 +422,10 @@ constexpr uint32_t kPeer = SML_FLAG_PEER_PLANES;   // the reader's half: acquire
 // per shard, W − 1 of them writing over xGMI).
 void XgmiSwitch::Quantize(ThreadPlanes& tp, const float* in, uint64_t n, hipStream_t st) {
     const uint64_t B = sml_num_blocks(n, P_);
-    sml_ok(sml_switch_exps(tp.peer_exps.data(), (uint16_t)W_, B, tp.gexp, kPeer, st), "sml_switch_exps");
+    sml_ok(sml_switch_exps(tp.peer_exps.data(), (uint16_t)W_, B, tp.gexp, kPeer, st), "sml_switch_exps", kWho);
     if (!push_) {
         sml_ok(sml_quantize_pack(in, n, P_, (uint16_t)W_, tp.gexp, tp.payload, nullptr, round_flags_, st),
-               "sml_quantize_pack");
+               "sml_quantize_pack", kWho);
         return;
     }
     const uint64_t S = (B + W_ - 1) / W_;
@@ -444,7 +436,7 @@ void XgmiSwitch::Quantize(ThreadPlanes& tp, const float* in, uint64_t n, hipStre
         const uint64_t n_el = std::min<uint64_t>(nb * P_, n - b0 * P_);
         int32_t* row = const_cast<int32_t*>(tp.peer_payload[w]) + (uint64_t)rank_ * S * P_;
         sml_ok(sml_quantize_pack(in + b0 * P_, n_el, P_, (uint16_t)W_, tp.gexp + b0, row, nullptr, round_flags_, st),
-               "sml_quantize_pack");
+               "sml_quantize_pack", kWho);
     }
 }
 
@@ -466,7 +458,7 @@ void XgmiSwitch::Aggregate(ThreadPlanes& tp, uint64_t n, hipStream_t st) {
     }
     sml_ok(sml_switch_aggregate(planes, exps, (uint16_t)W_, n_el, P_, nullptr, nullptr, tp.out + blk0 * P_, kPeer,
                                 st),
-           "sml_switch_aggregate");
+           "sml_switch_aggregate", kWho);
 }
 
 // A FLOAT32 slice, chunk by chunk, pipelined on two streams (the caller's
@@ -487,7 +479,7 @@ void XgmiSwitch::FloatSlice(int tid, const float* in, float* out, uint64_t numel
     ThreadPlanes& tp = planes_[tid];
     const uint64_t nchunks = (numel + cap_ - 1) / cap_;
     auto len = [&](uint64_t c) { return std::min<uint64_t>(cap_, numel - c * cap_); };
-    sml_ok(sml_exponents(in, len(0), P_, tp.exps, st), "sml_exponents");
+    sml_ok(sml_exponents(in, len(0), P_, tp.exps, st), "sml_exponents", kWho);
     release(st);
     StreamSync(st);
     Barrier(tid);
@@ -503,7 +495,7 @@ void XgmiSwitch::FloatSlice(int tid, const float* in, float* out, uint64_t numel
         if (push_) PushShard(tp, n, B, S, tp.xst);   // the multicast, as writes into the peers' out planes
         release(tp.xst);
         if (next) {
-            sml_ok(sml_exponents(in_next, len(c + 1), P_, tp.exps, st), "sml_exponents");
+            sml_ok(sml_exponents(in_next, len(c + 1), P_, tp.exps, st), "sml_exponents", kWho);
             release(st);
         }
         StreamSync(tp.xst);
@@ -512,7 +504,7 @@ void XgmiSwitch::FloatSlice(int tid, const float* in, float* out, uint64_t numel
         if (push_) {   // every shard is in the own out plane now: one local copy
             const void* src = tp.out;
             void* dst = out + c * cap_;
-            sml_ok(sml_copy_segments(&src, &dst, &n, 1, kPeer, tp.xst), "sml_copy_segments");
+            sml_ok(sml_copy_segments(&src, &dst, &n, 1, kPeer, tp.xst), "sml_copy_segments", kWho);
         } else {
             Gather(tp, out + c * cap_, n, B, S, tp.xst);
         }
@@ -546,7 +538,7 @@ void XgmiSwitch::PushShard(ThreadPlanes& tp, uint64_t n, uint64_t B, uint64_t S,
         cnt[k] = words;
         k++;
     }
-    sml_ok(sml_copy_segments(srcs, dsts, cnt, k, 0, st), "sml_copy_segments");
+    sml_ok(sml_copy_segments(srcs, dsts, cnt, k, 0, st), "sml_copy_segments", kWho);
 }
 
 // Worker w's shard of every plane (blocks [w S, min((w+1) S, B))) from its
@@ -565,14 +557,14 @@ void XgmiSwitch::Gather(ThreadPlanes& tp, void* out, uint64_t n, uint64_t B, uin
         words[k] = std::min<uint64_t>(nbw * P_, n - b0 * P_);
         k++;
     }
-    sml_ok(sml_copy_segments(srcs, dsts, words, k, kPeer, st), "sml_copy_segments");
+    sml_ok(sml_copy_segments(srcs, dsts, words, k, kPeer, st), "sml_copy_segments", kWho);
 }
 
 void XgmiSwitch::IntChunk(int tid, const int32_t* in, int32_t* out, uint64_t n, hipStream_t st) {
     ThreadPlanes& tp = planes_[tid];
     const uint64_t B = sml_num_blocks(n, P_);
     const uint64_t S = (B + W_ - 1) / W_;
-    sml_ok(sml_copy_words(in, tp.payload, n, st), "sml_copy_words");
+    sml_ok(sml_copy_words(in, tp.payload, n, st), "sml_copy_words", kWho);
     release(st);
     StreamSync(st);
     Barrier(tid);
@@ -584,7 +576,7 @@ void XgmiSwitch::IntChunk(int tid, const int32_t* in, int32_t* out, uint64_t n, 
         int32_t* dst = reinterpret_cast<int32_t*>(tp.out) + blk0 * P_;
         sml_ok(sml_switch_aggregate(planes, nullptr, (uint16_t)W_, nb * P_, P_, dst, nullptr, nullptr,
                                     SML_FLAG_PAYLOAD_LE | kPeer, st),
-               "sml_switch_aggregate");
+               "sml_switch_aggregate", kWho);
         release(st);
     }
     StreamSync(st);
