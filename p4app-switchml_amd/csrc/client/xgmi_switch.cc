@@ -27,7 +27,9 @@ constexpr int kMaxW = SML_MAX_SWITCH_WORKERS;
 constexpr int kMaxT = 16;
 constexpr size_t kHandle = sizeof(hipIpcMemHandle_t);
 
-constexpr const char* kWho = "xgmi switch: ";   // every hip_ok / sml_ok message here starts with it
+constexpr const char* kWho = "xgmi switch: ";   // every message here starts with it (hip_ok, sml_ok, Fatal)
+
+[[noreturn]] void Fatal(const std::string& what) { throw SwitchMLFatal(kWho + what); }
 
 // Reapers of wedged switches (XgmiSwitch::Wedged): how many are still
 // waiting for their streams to drain before they free what they hold.
@@ -79,6 +81,13 @@ XgmiShm* map_sized(int fd, int prot) {
     close(fd);
     return m == MAP_FAILED ? nullptr : static_cast<XgmiShm*>(m);
 }
+
+// A plane's IPC handle into its field of the segment (ShmPlanes).
+void export_plane(const void* plane, unsigned char* field) {
+    hipIpcMemHandle_t h;
+    hip_ok(hipIpcGetMemHandle(&h, const_cast<void*>(plane)), "hipIpcGetMemHandle", kWho);
+    memcpy(field, &h, kHandle);
+}
 }  // namespace
 
 // Worker 0 creates the segment (O_EXCL), replacing one left behind by a run
@@ -86,7 +95,6 @@ XgmiShm* map_sized(int fd, int prot) {
 // is alive.  So no worker joins a crashed run's barrier counts or handles.
 void XgmiSwitch::OpenSegment() {
     const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(timeout_ms_);
-    auto fail = [&](const std::string& what) { throw SwitchMLFatal("xgmi switch: " + what); };
     if (rank_ == 0) {
         for (int attempt = 0;; attempt++) {
             const int fd = shm_open(name_.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
@@ -96,7 +104,7 @@ void XgmiSwitch::OpenSegment() {
                 void* m = sized ? mmap(nullptr, sizeof(XgmiShm), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0)
                                 : MAP_FAILED;
                 close(fd);
-                if (m == MAP_FAILED) fail("mapping " + name_ + ": " + strerror(errno));
+                if (m == MAP_FAILED) Fatal("mapping " + name_ + ": " + strerror(errno));
                 shm_ = static_cast<XgmiShm*>(m);
                 shm_->W = (uint32_t)W_;
                 shm_->T = (uint32_t)T_;
@@ -107,7 +115,7 @@ void XgmiSwitch::OpenSegment() {
                 shm_->magic.store(kMagic, std::memory_order_release);
                 return;
             }
-            if (errno != EEXIST || attempt > 3) fail("shm_open " + name_ + ": " + strerror(errno));
+            if (errno != EEXIST || attempt > 3) Fatal("shm_open " + name_ + ": " + strerror(errno));
             const int fe = shm_open(name_.c_str(), O_RDONLY, 0600);
             if (fe >= 0) {
                 // a segment too short to hold the header is stale (its creator
@@ -116,11 +124,11 @@ void XgmiSwitch::OpenSegment() {
                     const int32_t pid = o->creator_pid.load();
                     munmap(o, sizeof(XgmiShm));
                     if (pid_alive(pid) && pid != getpid())
-                        fail("session " + name_ + " is in use by process " + std::to_string(pid) +
-                             " (pick another backend.xgmi.session)");
+                        Fatal("session " + name_ + " is in use by process " + std::to_string(pid) +
+                              " (pick another backend.xgmi.session)");
                 }
             }
-            fprintf(stderr, "[switchml] xgmi switch: replacing %s left behind by an earlier run\n", name_.c_str());
+            fprintf(stderr, "[switchml] %sreplacing %s left behind by an earlier run\n", kWho, name_.c_str());
             shm_unlink(name_.c_str());
         }
     }
@@ -141,7 +149,7 @@ void XgmiSwitch::OpenSegment() {
             }
         }
         if (std::chrono::steady_clock::now() > deadline)
-            fail("worker 0 did not open session " + name_ + " within backend.xgmi.timeout_ms");
+            Fatal("worker 0 did not open session " + name_ + " within backend.xgmi.timeout_ms");
         std::this_thread::sleep_for(std::chrono::milliseconds(1));
     }
 }
@@ -157,9 +165,9 @@ XgmiSwitch::XgmiSwitch(const Config& config, int device) {
     round_flags_ = config.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u;
     push_ = config.backend_.xgmi.push;
     fail_setup_ = config.backend_.xgmi.fail_setup;
-    if (W_ < 1 || W_ > kMaxW) throw SwitchMLFatal("xgmi switch: num_workers must be 1..16");
-    if (T_ < 1 || T_ > kMaxT) throw SwitchMLFatal("xgmi switch: num_worker_threads must be 1..16");
-    if (rank_ < 0 || rank_ >= W_) throw SwitchMLFatal("xgmi switch: general.rank must be < num_workers");
+    if (W_ < 1 || W_ > kMaxW) Fatal("num_workers must be 1..16");
+    if (T_ < 1 || T_ > kMaxT) Fatal("num_worker_threads must be 1..16");
+    if (rank_ < 0 || rank_ >= W_) Fatal("general.rank must be < num_workers");
     name_ = "/switchml-" + config.backend_.xgmi.session;
     try {
         Setup(device);
@@ -182,12 +190,11 @@ void XgmiSwitch::Setup(int device) {
         // mappings until its streams drain: wait for its reaper (bounded)
         std::unique_lock<std::mutex> lk(g_reap_mu);
         if (!g_reap_cv.wait_for(lk, std::chrono::milliseconds(timeout_ms_), [] { return g_reaping == 0; }))
-            throw SwitchMLFatal("xgmi switch: an earlier session's device work has not finished (its planes and "
-                                "peer mappings are still held); restart the process");
+            Fatal("an earlier session's device work has not finished (its planes and "
+                  "peer mappings are still held); restart the process");
     }
     OpenSegment();
-    if (shm_->attached.fetch_add(1) >= (uint32_t)W_)
-        throw SwitchMLFatal("xgmi switch: session " + name_ + " already has num_workers workers");
+    if (shm_->attached.fetch_add(1) >= (uint32_t)W_) Fatal("session " + name_ + " already has num_workers workers");
     attached_ = true;
 
     const uint64_t cap_b = (cap_ + 63) / 64 + 64;   // blocks at the smallest packet size, padded
@@ -196,19 +203,15 @@ void XgmiSwitch::Setup(int device) {
         ThreadPlanes& tp = planes_[t];
         hip_ok(hipMalloc(&tp.exps, cap_b), "hipMalloc", kWho);
         // + W packets of the largest size: the inbox's W rows of ceil(B / W)
-        // blocks may exceed B blocks by up to W - 1 (push form)
+        // blocks may exceed B blocks by up to W - 1 (push form; xgmi_shards.h)
         hip_ok(hipMalloc(&tp.payload, (cap_ + (uint64_t)kMaxW * 1024) * 4), "hipMalloc", kWho);
         hip_ok(hipMalloc(&tp.out, cap_ * 4), "hipMalloc", kWho);
         hip_ok(hipMalloc(&tp.gexp, cap_b), "hipMalloc", kWho);
         hip_ok(hipStreamCreateWithFlags(&tp.xst, hipStreamNonBlocking), "hipStreamCreate", kWho);
         ShmPlanes& sp = shm_->planes[rank_][t];
-        hipIpcMemHandle_t h;
-        hip_ok(hipIpcGetMemHandle(&h, tp.exps), "hipIpcGetMemHandle", kWho);
-        memcpy(sp.exps, &h, kHandle);
-        hip_ok(hipIpcGetMemHandle(&h, tp.payload), "hipIpcGetMemHandle", kWho);
-        memcpy(sp.payload, &h, kHandle);
-        hip_ok(hipIpcGetMemHandle(&h, tp.out), "hipIpcGetMemHandle", kWho);
-        memcpy(sp.out, &h, kHandle);
+        export_plane(tp.exps, sp.exps);
+        export_plane(tp.payload, sp.payload);
+        export_plane(tp.out, sp.out);
         sp.published.store(1, std::memory_order_release);
     }
     Barrier(kMaxT);   // every worker's handles are published
@@ -230,7 +233,17 @@ void XgmiSwitch::Setup(int device) {
             err = e.what();
         }
     Barrier(kMaxT);   // every worker is done importing
-    if (!err.empty()) throw SwitchMLFatal(err.rfind("xgmi switch: ", 0) == 0 ? err : "xgmi switch: " + err);
+    if (!err.empty()) throw SwitchMLFatal(err.rfind(kWho, 0) == 0 ? err : kWho + err);
+}
+
+// A peer's plane from its handle in the segment, recorded for ClosePeers.
+void* XgmiSwitch::ImportPlane(const unsigned char* field) {
+    void* p;
+    hipIpcMemHandle_t h;
+    memcpy(&h, field, kHandle);
+    hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle", kWho);
+    opened_.push_back(p);
+    return p;
 }
 
 // Map every peer's planes of every worker thread (hipIpc; over xGMI on a node).
@@ -248,23 +261,25 @@ void XgmiSwitch::OpenPeers() {
                 continue;
             }
             const ShmPlanes& sp = shm_->planes[w][t];
-            if (!sp.published.load(std::memory_order_acquire)) throw SwitchMLFatal("xgmi switch: peer planes missing");
-            void* p;
-            hipIpcMemHandle_t h;
-            memcpy(&h, sp.exps, kHandle);
-            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle", kWho);
-            opened_.push_back(p);
-            tp.peer_exps[w] = static_cast<const int8_t*>(p);
-            memcpy(&h, sp.payload, kHandle);
-            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle", kWho);
-            opened_.push_back(p);
-            tp.peer_payload[w] = static_cast<const int32_t*>(p);
-            memcpy(&h, sp.out, kHandle);
-            hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle", kWho);
-            opened_.push_back(p);
-            tp.peer_out[w] = static_cast<const float*>(p);
+            if (!sp.published.load(std::memory_order_acquire)) Fatal("peer planes missing");
+            tp.peer_exps[w] = static_cast<const int8_t*>(ImportPlane(sp.exps));
+            tp.peer_payload[w] = static_cast<const int32_t*>(ImportPlane(sp.payload));
+            tp.peer_out[w] = static_cast<const float*>(ImportPlane(sp.out));
         }
     }
+}
+
+void XgmiSwitch::ClosePeers(std::vector<void*>& opened) {
+    for (void* p : opened) (void)hipIpcCloseMemHandle(p);
+    opened.clear();
+}
+
+void XgmiSwitch::FreePlanes(ThreadPlanes& tp) {
+    (void)hipFree(tp.exps);
+    (void)hipFree(tp.payload);
+    (void)hipFree(tp.out);
+    (void)hipFree(tp.gexp);
+    if (tp.xst) (void)hipStreamDestroy(tp.xst);
 }
 
 // Everything this worker holds, in reverse order of Setup; safe on a
@@ -274,8 +289,8 @@ void XgmiSwitch::Release() {
         // device work that has not finished may still use the planes, the
         // peer mappings and the streams: a detached reaper frees them once
         // every stream involved has drained (never, if the device is hung)
-        fprintf(stderr, "[switchml] xgmi switch: device work did not finish; %zu planes and %zu peer mappings "
-                        "are freed once it does\n", planes_.size() * 4, opened_.size());
+        fprintf(stderr, "[switchml] %sdevice work did not finish; %zu planes and %zu peer mappings "
+                        "are freed once it does\n", kWho, planes_.size() * 4, opened_.size());
         struct Remains {
             std::vector<ThreadPlanes> planes;
             std::vector<void*> opened;
@@ -294,29 +309,16 @@ void XgmiSwitch::Release() {
                 if (tp.stuck) (void)hipStreamSynchronize(tp.stuck);
                 if (tp.xst) (void)hipStreamSynchronize(tp.xst);
             }
-            for (void* p : rem->opened) (void)hipIpcCloseMemHandle(p);
-            for (ThreadPlanes& tp : rem->planes) {
-                (void)hipFree(tp.exps);
-                (void)hipFree(tp.payload);
-                (void)hipFree(tp.out);
-                (void)hipFree(tp.gexp);
-                if (tp.xst) (void)hipStreamDestroy(tp.xst);
-            }
+            ClosePeers(rem->opened);
+            for (ThreadPlanes& tp : rem->planes) FreePlanes(tp);
             delete rem;
             std::lock_guard<std::mutex> lk(g_reap_mu);
             g_reaping--;
             g_reap_cv.notify_all();
         }).detach();
     }
-    for (void* p : opened_) (void)hipIpcCloseMemHandle(p);
-    opened_.clear();
-    for (ThreadPlanes& tp : planes_) {
-        (void)hipFree(tp.exps);
-        (void)hipFree(tp.payload);
-        (void)hipFree(tp.out);
-        (void)hipFree(tp.gexp);
-        if (tp.xst) (void)hipStreamDestroy(tp.xst);
-    }
+    ClosePeers(opened_);
+    for (ThreadPlanes& tp : planes_) FreePlanes(tp);
     planes_.clear();
     if (!shm_) return;
     bool last = false;
@@ -337,8 +339,7 @@ XgmiSwitch::~XgmiSwitch() {
             Barrier(kMaxT);   // nobody reads a peer's planes any more
         } catch (...) {
         }
-        for (void* p : opened_) (void)hipIpcCloseMemHandle(p);
-        opened_.clear();
+        ClosePeers(opened_);
         try {
             Barrier(kMaxT);   // every mapping of our planes is closed
         } catch (...) {
@@ -355,13 +356,16 @@ void XgmiSwitch::Poison() {
     if (shm_) shm_->poisoned.store(1, std::memory_order_release);
 }
 
+void XgmiSwitch::ThrowIfPoisoned() {
+    if (shm_->poisoned.load(std::memory_order_acquire)) Fatal("the session failed on another worker");
+}
+
 // Sense-reversing barrier over the W workers (one per worker thread, so the
 // T slices of a job are exchanged independently).  Polls; a worker that does
 // not arrive within backend.xgmi.timeout_ms fails the slice.
 void XgmiSwitch::Barrier(int index) {
     ShmBarrier& b = shm_->bar[index];
-    if (shm_->poisoned.load(std::memory_order_acquire))
-        throw SwitchMLFatal("xgmi switch: the session failed on another worker");
+    ThrowIfPoisoned();
     const uint32_t g = b.gen.load(std::memory_order_acquire);
     if (b.count.fetch_add(1, std::memory_order_acq_rel) + 1 == (uint32_t)W_) {
         b.count.store(0, std::memory_order_relaxed);
@@ -377,11 +381,10 @@ void XgmiSwitch::Barrier(int index) {
                 // A worker that failed mid-exchange poisons the session: its
                 // arrival (or absence) would put every later barrier of this
                 // thread index out of phase, so nobody proceeds past it.
-                if (shm_->poisoned.load(std::memory_order_acquire))
-                    throw SwitchMLFatal("xgmi switch: the session failed on another worker");
+                ThrowIfPoisoned();
                 if (std::chrono::steady_clock::now() > deadline) {
                     Poison();
-                    throw SwitchMLFatal("xgmi switch: barrier timeout (a worker did not arrive)");
+                    Fatal("barrier timeout (a worker did not arrive)");
                 }
             }
         }
@@ -403,7 +406,7 @@ bool XgmiSwitch::StreamSync(hipStream_t st, bool bounded_only) {
             if ((spins & 1023) == 0 && std::chrono::steady_clock::now() > deadline) {
                 wedged_.store(true, std::memory_order_release);
                 if (bounded_only) return false;
-                throw SwitchMLFatal("xgmi switch: device work did not finish within backend.xgmi.timeout_ms");
+                Fatal("device work did not finish within backend.xgmi.timeout_ms");
             }
         }
     }
@@ -416,49 +419,51 @@ void release(hipStream_t st) { sml_ok(sml_release_to_peers(st), "sml_release_to_
 constexpr uint32_t kPeer = SML_FLAG_PEER_PLANES;   // the reader's half: acquire in the reading kernels
 }  // namespace
 
+// The end of every phase of an exchange: release what the phase wrote for
+// the peers, wait (bounded) for every stream the phase used, in the order
+// given, then meet the peers at worker thread tid's barrier.
+void XgmiSwitch::HandOff(int tid, std::initializer_list<PhaseStream> streams) {
+    for (const PhaseStream& s : streams)
+        if (s.release) release(s.st);
+    for (const PhaseStream& s : streams) StreamSync(s.st);
+    Barrier(tid);
+}
+
 // The switch's exponent max over the W planes into gexp, then K3: quantize
 // with the global exponents into the own BE payload plane (pull), or each
 // shard w straight into row `rank` of worker w's inbox (push: one K3 launch
 // per shard, W − 1 of them writing over xGMI).
-void XgmiSwitch::Quantize(ThreadPlanes& tp, const float* in, uint64_t n, hipStream_t st) {
-    const uint64_t B = sml_num_blocks(n, P_);
-    sml_ok(sml_switch_exps(tp.peer_exps.data(), (uint16_t)W_, B, tp.gexp, kPeer, st), "sml_switch_exps", kWho);
+void XgmiSwitch::Quantize(ThreadPlanes& tp, const float* in, const ShardPlan& plan, hipStream_t st) {
+    const uint16_t W = (uint16_t)W_;
+    sml_ok(sml_switch_exps(tp.peer_exps.data(), W, plan.B, tp.gexp, kPeer, st), "sml_switch_exps", kWho);
     if (!push_) {
-        sml_ok(sml_quantize_pack(in, n, P_, (uint16_t)W_, tp.gexp, tp.payload, nullptr, round_flags_, st),
+        sml_ok(sml_quantize_pack(in, plan.n, P_, W, tp.gexp, tp.payload, nullptr, round_flags_, st),
                "sml_quantize_pack", kWho);
         return;
     }
-    const uint64_t S = (B + W_ - 1) / W_;
     for (int w = 0; w < W_; w++) {
-        const uint64_t b0 = std::min<uint64_t>((uint64_t)w * S, B);
-        const uint64_t nb = std::min<uint64_t>(S, B - b0);
-        if (!nb) continue;
-        const uint64_t n_el = std::min<uint64_t>(nb * P_, n - b0 * P_);
-        int32_t* row = const_cast<int32_t*>(tp.peer_payload[w]) + (uint64_t)rank_ * S * P_;
-        sml_ok(sml_quantize_pack(in + b0 * P_, n_el, P_, (uint16_t)W_, tp.gexp + b0, row, nullptr, round_flags_, st),
+        const Shard sh = plan.shard(w);
+        if (!sh.nb) continue;
+        int32_t* row = const_cast<int32_t*>(tp.peer_payload[w]) + plan.inbox_row(rank_);
+        sml_ok(sml_quantize_pack(in + sh.offset, sh.numel, P_, W, tp.gexp + sh.b0, row, nullptr, round_flags_, st),
                "sml_quantize_pack", kWho);
     }
 }
 
 // K6: the wrapping sum of this worker's shard over the W planes, dequantized
 // into the own output plane.
-void XgmiSwitch::Aggregate(ThreadPlanes& tp, uint64_t n, hipStream_t st) {
-    const uint64_t B = sml_num_blocks(n, P_);
-    const uint64_t S = (B + W_ - 1) / W_;
-    const uint64_t blk0 = std::min<uint64_t>((uint64_t)rank_ * S, B);
-    const uint64_t nb = std::min<uint64_t>(S, B - blk0);
-    if (!nb) return;
-    const uint64_t n_el = std::min<uint64_t>(nb * P_, n - blk0 * P_);
+void XgmiSwitch::Aggregate(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st) {
+    const Shard sh = plan.shard(rank_);
+    if (!sh.nb) return;
     const int32_t* planes[kMaxW];
     const int8_t* exps[kMaxW];
     for (int w = 0; w < W_; w++) {
         // pull: worker w's plane at this shard; push: row w of the own inbox
-        planes[w] = push_ ? tp.payload + (uint64_t)w * S * P_ : tp.peer_payload[w] + blk0 * P_;
-        exps[w] = tp.gexp + blk0;
+        planes[w] = push_ ? tp.payload + plan.inbox_row(w) : tp.peer_payload[w] + sh.offset;
+        exps[w] = tp.gexp + sh.b0;
     }
-    sml_ok(sml_switch_aggregate(planes, exps, (uint16_t)W_, n_el, P_, nullptr, nullptr, tp.out + blk0 * P_, kPeer,
-                                st),
-           "sml_switch_aggregate", kWho);
+    sml_ok(sml_switch_aggregate(planes, exps, (uint16_t)W_, sh.numel, P_, nullptr, nullptr, tp.out + sh.offset,
+                                kPeer, st), "sml_switch_aggregate", kWho);
 }
 
 // A FLOAT32 slice, chunk by chunk, pipelined on two streams (the caller's
@@ -475,46 +480,43 @@ void XgmiSwitch::Aggregate(ThreadPlanes& tp, uint64_t n, hipStream_t st) {
 // the next chunk); payload (peers' K6(c), phase 1) before K3(c+1) (phase 2);
 // out (peers' gather(c), phase 2) before K6(c+1); gexp (own K6(c)) before
 // the max of chunk c+1.  So one set of planes serves the pipeline.
+// Each "| barrier" is one HandOff.  What xst wrote for the peers (K6's shard)
+// is released as soon as it is queued, before the next chunk's work is
+// enqueued on st; the gather writes the caller's tensor, which no peer reads.
 void XgmiSwitch::FloatSlice(int tid, const float* in, float* out, uint64_t numel, hipStream_t st) {
     ThreadPlanes& tp = planes_[tid];
+    const hipStream_t xst = tp.xst;
     const uint64_t nchunks = (numel + cap_ - 1) / cap_;
-    auto len = [&](uint64_t c) { return std::min<uint64_t>(cap_, numel - c * cap_); };
-    sml_ok(sml_exponents(in, len(0), P_, tp.exps, st), "sml_exponents", kWho);
-    release(st);
-    StreamSync(st);
-    Barrier(tid);
-    Quantize(tp, in, len(0), st);
-    release(st);
-    StreamSync(st);
-    Barrier(tid);
+    auto plan = [&](uint64_t c) { return ShardPlan(std::min<uint64_t>(cap_, numel - c * cap_), P_, (uint64_t)W_); };
+    auto k2 = [&](uint64_t c) {
+        sml_ok(sml_exponents(in + c * cap_, plan(c).n, P_, tp.exps, st), "sml_exponents", kWho);
+    };
+    auto k3 = [&](uint64_t c) { Quantize(tp, in + c * cap_, plan(c), st); };   // the max, then K3
+    auto k6 = [&](uint64_t c) {
+        Aggregate(tp, plan(c), xst);
+        if (push_) PushShard(tp, plan(c), xst);   // the multicast, as writes into the peers' out planes
+        release(xst);
+    };
+    auto gather = [&](uint64_t c) {
+        if (!push_) return Gather(tp, out + c * cap_, plan(c), xst);
+        // every shard is in the own out plane now: one local copy
+        const void* src = tp.out;
+        void* dst = out + c * cap_;
+        const uint64_t n = plan(c).n;
+        sml_ok(sml_copy_segments(&src, &dst, &n, 1, kPeer, xst), "sml_copy_segments", kWho);
+    };
+    k2(0);
+    HandOff(tid, {{st, true}});
+    k3(0);
+    HandOff(tid, {{st, true}});
     for (uint64_t c = 0; c < nchunks; c++) {
-        const uint64_t n = len(c), B = sml_num_blocks(n, P_), S = (B + W_ - 1) / W_;
         const bool next = c + 1 < nchunks;
-        const float* in_next = in + (c + 1) * cap_;
-        Aggregate(tp, n, tp.xst);
-        if (push_) PushShard(tp, n, B, S, tp.xst);   // the multicast, as writes into the peers' out planes
-        release(tp.xst);
-        if (next) {
-            sml_ok(sml_exponents(in_next, len(c + 1), P_, tp.exps, st), "sml_exponents", kWho);
-            release(st);
-        }
-        StreamSync(tp.xst);
-        StreamSync(st);
-        Barrier(tid);
-        if (push_) {   // every shard is in the own out plane now: one local copy
-            const void* src = tp.out;
-            void* dst = out + c * cap_;
-            sml_ok(sml_copy_segments(&src, &dst, &n, 1, kPeer, tp.xst), "sml_copy_segments", kWho);
-        } else {
-            Gather(tp, out + c * cap_, n, B, S, tp.xst);
-        }
-        if (next) {
-            Quantize(tp, in_next, len(c + 1), st);
-            release(st);
-        }
-        StreamSync(tp.xst);
-        StreamSync(st);
-        Barrier(tid);   // peers are done reading our planes before they are written again
+        k6(c);
+        if (next) k2(c + 1);
+        HandOff(tid, {{xst, false}, {st, next}});
+        gather(c);
+        if (next) k3(c + 1);
+        HandOff(tid, {{xst, false}, {st, next}});   // peers are done reading our planes before they are written again
     }
 }
 
@@ -522,20 +524,18 @@ void XgmiSwitch::FloatSlice(int tid, const float* in, float* out, uint64_t numel
 // out plane) written into the same place of every peer's out plane (W − 1
 // segments in one launch, over xGMI), so that after the next barrier every
 // out plane holds all W shards.
-void XgmiSwitch::PushShard(ThreadPlanes& tp, uint64_t n, uint64_t B, uint64_t S, hipStream_t st) {
-    const uint64_t b0 = std::min<uint64_t>((uint64_t)rank_ * S, B);
-    const uint64_t nb = std::min<uint64_t>(S, B - b0);
-    if (!nb || W_ == 1) return;
-    const uint64_t words = std::min<uint64_t>(nb * P_, n - b0 * P_);
+void XgmiSwitch::PushShard(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st) {
+    const Shard sh = plan.shard(rank_);
+    if (!sh.nb || W_ == 1) return;
     const void* srcs[kMaxW];
     void* dsts[kMaxW];
     uint64_t cnt[kMaxW];
     uint32_t k = 0;
     for (int w = 0; w < W_; w++) {
         if (w == rank_) continue;
-        srcs[k] = tp.out + b0 * P_;
-        dsts[k] = const_cast<float*>(tp.peer_out[w]) + b0 * P_;
-        cnt[k] = words;
+        srcs[k] = tp.out + sh.offset;
+        dsts[k] = const_cast<float*>(tp.peer_out[w]) + sh.offset;
+        cnt[k] = sh.numel;
         k++;
     }
     sml_ok(sml_copy_segments(srcs, dsts, cnt, k, 0, st), "sml_copy_segments", kWho);
@@ -543,60 +543,57 @@ void XgmiSwitch::PushShard(ThreadPlanes& tp, uint64_t n, uint64_t B, uint64_t S,
 
 // Worker w's shard of every plane (blocks [w S, min((w+1) S, B))) from its
 // out plane into `out`, one sml_copy_segments launch for the W shards.
-void XgmiSwitch::Gather(ThreadPlanes& tp, void* out, uint64_t n, uint64_t B, uint64_t S, hipStream_t st) {
+void XgmiSwitch::Gather(ThreadPlanes& tp, void* out, const ShardPlan& plan, hipStream_t st) {
     const void* srcs[kMaxW];
     void* dsts[kMaxW];
     uint64_t words[kMaxW];
     uint32_t k = 0;
     for (int w = 0; w < W_; w++) {
-        const uint64_t b0 = std::min<uint64_t>((uint64_t)w * S, B);
-        const uint64_t nbw = std::min<uint64_t>(S, B - b0);
-        if (!nbw) continue;
-        srcs[k] = reinterpret_cast<const uint32_t*>(tp.peer_out[w]) + b0 * P_;
-        dsts[k] = static_cast<uint32_t*>(out) + b0 * P_;
-        words[k] = std::min<uint64_t>(nbw * P_, n - b0 * P_);
+        const Shard sh = plan.shard(w);
+        if (!sh.nb) continue;
+        srcs[k] = reinterpret_cast<const uint32_t*>(tp.peer_out[w]) + sh.offset;
+        dsts[k] = static_cast<uint32_t*>(out) + sh.offset;
+        words[k] = sh.numel;
         k++;
     }
     sml_ok(sml_copy_segments(srcs, dsts, words, k, kPeer, st), "sml_copy_segments", kWho);
 }
 
+// An INT32 chunk, on the caller's stream alone:
+//   copy into the own payload plane | barrier | sum of the own shard into
+//   the own out plane | barrier | gather | barrier
+// The sum runs over the shard's whole blocks (inside the planes: a chunk is
+// at most cap_ words, a multiple of P); the gather copies the n words.  The
+// last barrier keeps the planes from being rewritten (the next chunk's copy)
+// while a peer still gathers from them; it hands nothing off, so no release.
 void XgmiSwitch::IntChunk(int tid, const int32_t* in, int32_t* out, uint64_t n, hipStream_t st) {
     ThreadPlanes& tp = planes_[tid];
-    const uint64_t B = sml_num_blocks(n, P_);
-    const uint64_t S = (B + W_ - 1) / W_;
+    const ShardPlan plan(n, P_, (uint64_t)W_);
+    const Shard sh = plan.shard(rank_);
     sml_ok(sml_copy_words(in, tp.payload, n, st), "sml_copy_words", kWho);
-    release(st);
-    StreamSync(st);
-    Barrier(tid);
-    const uint64_t blk0 = std::min<uint64_t>((uint64_t)rank_ * S, B);
-    const uint64_t nb = std::min<uint64_t>(S, B - blk0);
-    if (nb) {
+    HandOff(tid, {{st, true}});
+    if (sh.nb) {
         const int32_t* planes[kMaxW];
-        for (int w = 0; w < W_; w++) planes[w] = tp.peer_payload[w] + blk0 * P_;
-        int32_t* dst = reinterpret_cast<int32_t*>(tp.out) + blk0 * P_;
-        sml_ok(sml_switch_aggregate(planes, nullptr, (uint16_t)W_, nb * P_, P_, dst, nullptr, nullptr,
-                                    SML_FLAG_PAYLOAD_LE | kPeer, st),
-               "sml_switch_aggregate", kWho);
-        release(st);
+        for (int w = 0; w < W_; w++) planes[w] = tp.peer_payload[w] + sh.offset;
+        int32_t* dst = reinterpret_cast<int32_t*>(tp.out) + sh.offset;
+        sml_ok(sml_switch_aggregate(planes, nullptr, (uint16_t)W_, sh.words, P_, dst, nullptr, nullptr,
+                                    SML_FLAG_PAYLOAD_LE | kPeer, st), "sml_switch_aggregate", kWho);
     }
-    StreamSync(st);
-    Barrier(tid);
-    Gather(tp, out, n, B, S, st);
-    StreamSync(st);
-    Barrier(tid);
+    HandOff(tid, {{st, sh.nb != 0}});
+    Gather(tp, out, plan, st);
+    HandOff(tid, {{st, false}});
 }
 
 void XgmiSwitch::AllReduceSlice(int tid, const void* in, void* out, uint64_t numel, DataType type, hipStream_t st) {
-    if (tid < 0 || tid >= T_) throw SwitchMLFatal("xgmi switch: bad worker thread id");
+    if (tid < 0 || tid >= T_) Fatal("bad worker thread id");
     // every worker refuses the same job here, before any barrier (the CollNet
     // plugin never posts one: its reduceSupport is 0 for these types under xgmi)
     if (IsHalfType(type))
-        throw SwitchMLFatal(std::string("xgmi switch: ") + DataTypeName(type) +
-                            " jobs are not supported with backend = xgmi; use backend = dummy (mode bulk or fused)");
+        Fatal(std::string(DataTypeName(type)) +
+              " jobs are not supported with backend = xgmi; use backend = dummy (mode bulk or fused)");
     if (numel == 0) return;
-    if (Wedged()) throw SwitchMLFatal("xgmi switch: an earlier slice's device work did not finish");
-    if (shm_->poisoned.load(std::memory_order_acquire))
-        throw SwitchMLFatal("xgmi switch: the session failed on another worker");
+    if (Wedged()) Fatal("an earlier slice's device work did not finish");
+    ThrowIfPoisoned();
     try {
         if (type == FLOAT32) {
             FloatSlice(tid, static_cast<const float*>(in), static_cast<float*>(out), numel, st);

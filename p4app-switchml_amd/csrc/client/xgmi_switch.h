@@ -27,7 +27,9 @@
 //     and chunk c's gather beside chunk c + 1's exponent max and K3 (local
 //     HBM work beside the xGMI phases), two barriers per chunk; one set of
 //     planes suffices because every plane's readers finish one phase before
-//     its next writer starts (xgmi_switch.cc, FloatSlice);
+//     its next writer starts (xgmi_switch.cc, FloatSlice); which blocks each
+//     worker's shard holds is xgmi_shards.h, and every phase ends in HandOff
+//     (release to the peers, bounded stream sync, barrier);
 //   * push form (backend.xgmi.push): K3 writes each shard of the quantized
 //     payload straight into its owner's inbox plane (W − 1 shards over xGMI,
 //     posted writes) and K6 reads the W rows of the own inbox from local HBM;
@@ -49,11 +51,13 @@
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "config.h"
+#include "xgmi_shards.h"
 
 namespace switchml {
 
@@ -120,21 +124,35 @@ class XgmiSwitch {
         hipStream_t stuck = nullptr;   // the caller's stream, abandoned with work queued (NoteStuckStream)
     };
 
+    // One stream of a phase's hand-off (HandOff): `release` when the phase
+    // queued work on it whose output the peers read next.
+    struct PhaseStream {
+        hipStream_t st;
+        bool release;
+    };
+
     void OpenSegment();
     void Setup(int device);
     void OpenPeers();
+    void* ImportPlane(const unsigned char* field);
+    // What Release and a wedged switch's reaper both do, in this order.
+    static void ClosePeers(std::vector<void*>& opened);
+    static void FreePlanes(ThreadPlanes& tp);
     void Release();
+    void ThrowIfPoisoned();
     void Barrier(int index);
     // Wait for the work queued on `st`, polling against backend.xgmi.timeout_ms
     // (a device that never finishes fails the slice instead of blocking the
     // worker thread forever); `bounded_only` waits never throw (cleanup paths).
     bool StreamSync(hipStream_t st, bool bounded_only = false);
+    void HandOff(int tid, std::initializer_list<PhaseStream> streams);
+    // The chunk's shards (which blocks each worker owns) come from xgmi_shards.h.
     void FloatSlice(int tid, const float* in, float* out, uint64_t numel, hipStream_t st);
-    void Aggregate(ThreadPlanes& tp, uint64_t n, hipStream_t st);
-    void Quantize(ThreadPlanes& tp, const float* in, uint64_t n, hipStream_t st);
+    void Aggregate(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st);
+    void Quantize(ThreadPlanes& tp, const float* in, const ShardPlan& plan, hipStream_t st);
     void IntChunk(int tid, const int32_t* in, int32_t* out, uint64_t n, hipStream_t st);
-    void Gather(ThreadPlanes& tp, void* out, uint64_t n, uint64_t B, uint64_t S, hipStream_t st);
-    void PushShard(ThreadPlanes& tp, uint64_t n, uint64_t B, uint64_t S, hipStream_t st);
+    void Gather(ThreadPlanes& tp, void* out, const ShardPlan& plan, hipStream_t st);
+    void PushShard(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st);
 
     int rank_, W_, T_;
     int device_ = -1;
