@@ -201,9 +201,13 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
  * at any element) and no byte outside [ptr, ptr + 2 * numel) is touched;
  * payload planes 16-byte aligned, as above.  in == out is allowed for the
  * round trip.  Batches of 16-bit slices go through
- * sml_roundtrip_loopback_batch_typed (below); the burst, frames and RDMA
- * entry points and sml_roundtrip_loopback_batch take no 16-bit type (a burst
- * whose data_type is one returns SML_ERR_UNSUPPORTED). */
+ * sml_roundtrip_loopback_batch_typed (below), DPDK frames through
+ * sml_quantize_pack_frames_typed / sml_dequantize_frames_typed (with the
+ * frames, below).  A 16-bit slice's RDMA messages need no entry point of
+ * their own: sml_quantize_pack_typed at packet_numel = msg_numel gives the
+ * message payloads and sml_rdma_imm on its exponent plane the immediates.
+ * The burst entry points and sml_roundtrip_loopback_batch take no 16-bit type
+ * (a burst whose data_type is one returns SML_ERR_UNSUPPORTED). */
 sml_status_t sml_exponents_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
                                  uint32_t packet_numel, int8_t* d_exps, void* stream);
 sml_status_t sml_quantize_pack_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
@@ -416,7 +420,8 @@ typedef struct sml_frame_params {
 uint64_t sml_frame_bytes(uint32_t packet_numel);
 
 /* Words of the per-slice rx state (d_state) a receive call needs: FLOAT32
- * (sml_dequantize_frames) max(1, B + b) with b = min(batch_max, B); INT32
+ * (sml_dequantize_frames; FLOAT16 / BFLOAT16 through
+ * sml_dequantize_frames_typed alike) max(1, B + b) with b = min(batch_max, B); INT32
  * (sml_unpack_frames_int32, int32 != 0) 2B + 6.  B = ceil(numel / P). */
 uint64_t sml_rx_state_words(uint64_t numel, uint32_t packet_numel, uint32_t batch_max, int int32);
 
@@ -461,6 +466,43 @@ sml_status_t sml_dequantize_frames(const void* frames, uint64_t num_frames, uint
                                    uint32_t batch_max, uint64_t job_id, int8_t* d_exps,
                                    uint64_t* d_state, float* d_out, uint64_t* d_counts,
                                    void* stream);
+
+/* FLOAT16 / BFLOAT16 job slices over the same frames: the argument lists of
+ * sml_quantize_pack_frames and sml_dequantize_frames with void* for the typed
+ * buffer and its sml_data_type_t next to it, by the convention of the other
+ * sml_*_typed entry points (above).
+ *   SML_FLOAT16 / SML_BFLOAT16: the kernels convert.  tx: x32[i] = (float)x[i]
+ *     (exact) right after the load, and the frame set is byte for byte the
+ *     one sml_quantize_pack_frames builds from x32 — headers (job_type_size
+ *     and short_job_id included), pkt_ids, pool indices, exponent bytes, the
+ *     zero payload of the extra batch, BE int32 words, zero tail words of a
+ *     partial last block.  The wire format knows no element size:
+ *     B = ceil(numel / P) and b = min(batch_max, B) as for FLOAT32.  rx: the
+ *     claim, the state words, the first-copy-wins rule, d_exps and d_counts
+ *     are sml_dequantize_frames'; an accepted payload is dequantized to an
+ *     fp32 y32 as there and stored as (T)y32, round to nearest even (overflow
+ *     -> +-inf, fp16 results below the normal range -> fp16 denormals, NaN ->
+ *     a NaN of T); a block without a winner in the call keeps its bytes.
+ *   SML_FLOAT32: exactly sml_quantize_pack_frames / sml_dequantize_frames
+ *     (same kernels, same bytes).
+ *   SML_INT32 (or any other value): SML_ERR_UNSUPPORTED.
+ * A 16-bit buffer needs 2-byte alignment only (a slice starts at any element)
+ * and no byte outside [ptr, ptr + 2 * numel) is read (tx) or written (rx).
+ * One that is not 2-byte aligned gets what the FLOAT32 entry point gives a
+ * buffer that is not 4-byte aligned: SML_ERR_INVALID_ARG (tx),
+ * SML_ERR_ALIGNMENT (rx).  Every check happens before anything is launched.
+ * sml_rx_state_words (int32 = 0) and sml_rx_reset serve a 16-bit slice as
+ * they are: the state is per pkt_id and knows no element type. */
+sml_status_t sml_quantize_pack_frames_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
+                                            uint32_t packet_numel, uint16_t num_workers,
+                                            const int8_t* d_global_exps, uint32_t batch_max,
+                                            const sml_frame_params* params, void* frames,
+                                            uint64_t frame_stride, void* stream);
+sml_status_t sml_dequantize_frames_typed(const void* frames, uint64_t num_frames, uint64_t frame_stride,
+                                         uint64_t numel, uint32_t packet_numel, uint16_t num_workers,
+                                         uint32_t batch_max, uint64_t job_id, int8_t* d_exps,
+                                         uint64_t* d_state, void* d_out, sml_data_type_t data_type,
+                                         uint64_t* d_counts, void* stream);
 
 /* INT32 job slices (DataType::INT32, common.h:51-55) over the same frames.
  * The INT32 pre/post-processor only reorders bytes and needs no extra batch
@@ -567,8 +609,10 @@ uint32_t sml_set_stream_tile_slices(uint32_t slices);
  * sml_roundtrip_loopback_batch (by the batch's total output), the typed
  * output of their sml_*_typed counterparts (by its bytes;
  * sml_roundtrip_loopback_batch_typed by the call's total output over every
- * slice and type), the fp32 output of sml_dequantize_frames, the payloads of a device-memory frame set
- * of sml_quantize_pack_frames (host frame sets keep default stores) and the
+ * slice and type), the fp32 output of sml_dequantize_frames (the typed output
+ * of sml_dequantize_frames_typed by its bytes, 2 * numel for a 16-bit type),
+ * the payloads of a device-memory frame set of sml_quantize_pack_frames and
+ * sml_quantize_pack_frames_typed (host frame sets keep default stores) and the
  * sml_stream_copy probe; default 64 MiB, a quarter of the 256 MiB Infinity
  * Cache — DESIGN.md §4); UINT64_MAX = never, 0 = always.
  * Results are identical either way.  Returns the previous value. */

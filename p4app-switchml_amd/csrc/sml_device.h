@@ -1,7 +1,9 @@
 // sml_device.h — device-side building blocks shared by the gfx950 kernels of
 // SwitchML's end-host pre/post-processor (sml_planes.h: the plane kernel
 // templates, sml_quantizer.hip: fp32 planes, sml_half.hip: 16-bit planes;
-// sml_frames.hip: DPDK frames; sml_switch.hip: the in-node switch).
+// sml_frame_kernels.h: the DPDK frame kernel templates, sml_frames.hip: fp32 /
+// INT32 frames, sml_frames_half.hip: 16-bit frames; sml_switch.hip: the
+// in-node switch).
 //
 // What the reference does per 1 KiB LTU on one CPU thread
 // (client_lib/src/prepostprocessors/cpu_exponent_quantizer_ppp.cc, "ppp.cc"),

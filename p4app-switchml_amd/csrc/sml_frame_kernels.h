@@ -1,0 +1,415 @@
+// sml_frame_kernels.h — the DPDK frame kernels that touch a job slice's typed
+// buffer, as templates on the element policy E (ElemF32<ALIGNED> / Elem16<H>,
+// sml_device.h): the transmit side's fused quantize + pack into frames and the
+// receive side's apply pass.  sml_frames.hip instantiates them for FLOAT32 and
+// INT32 and holds the entry points and the kernels that see no element (the
+// claim pass, the INT32 receive loop); sml_frames_half.hip instantiates them
+// for FLOAT16 / BFLOAT16, so the two units build in parallel.  An element is
+// widened to fp32 by E's loads and narrowed by its stores; everything between
+// — and the wire format — is the same code for every type.
+#ifndef SML_FRAME_KERNELS_H_
+#define SML_FRAME_KERNELS_H_
+
+#include "sml_host.h"
+
+namespace sml {
+
+// ---------------------------------------------------------- DPDK frames
+
+struct FrameArgs {
+    const void* in;         // the slice: E::raw elements (INT32: words moved as bits)
+    uint64_t numel;
+    uint64_t nblocks;       // B
+    uint64_t ntiles;        // ceil(B*P / 1024)
+    uint64_t b;             // extra-batch size = min(batch_max, B)
+    const int8_t* gexp;     // global exponents or nullptr
+    uint8_t* frames;        // B + b frames, 4-byte aligned
+    uint64_t stride;        // bytes between frames, multiple of 4
+    uint32_t W;
+    uint32_t xcd;           // xcd_block chunk (0 = plain order)
+    uint32_t pool_start, pool_shift, mop;
+    uint32_t hdr[11];       // frame bytes 0..43: Eth, IPv4, UDP, job_type_size, short_job_id
+};
+
+// PktId2PoolIndex, dpdk_worker_thread_utils.inc:42-52.
+__device__ __forceinline__ uint32_t pool_index(uint64_t p, const FrameArgs& a) {
+    const uint32_t i = (uint32_t)((p + a.pool_shift) % (2ull * a.mop));
+    return i < a.mop ? ((a.pool_start + i) & 0xffffu) : (((a.pool_start + (i - a.mop)) | 0x8000u) & 0xffffu);
+}
+
+// Lanes 0..12 write the 52 header bytes of frame p (one dword each):
+// dwords 0-10 constant, 11 = pkt_id (host order), 12 = pool index (BE16),
+// exponent byte, zero byte.  (Extra-batch frames; the bulk of the headers is
+// written lane-parallel by k_quantize_frames.)
+__device__ __forceinline__ void write_frame_header(const FrameArgs& a, uint64_t p, int lane, uint32_t exp_byte) {
+    if (lane > 12) return;
+    uint32_t dw = a.hdr[0];
+#pragma unroll
+    for (int i = 1; i < 11; i++) dw = lane == i ? a.hdr[i] : dw;
+    if (lane == 11) dw = (uint32_t)p;
+    if (lane == 12) {
+        const uint32_t pool = pool_index(p, a);
+        dw = (pool >> 8) | ((pool & 0xffu) << 8) | ((exp_byte & 0xffu) << 16);
+    }
+    *reinterpret_cast<uint32_t*>(a.frames + p * a.stride + 4 * lane) = dw;
+}
+
+// Fused quantize + pack into DPDK frames (BuildPacket + PreprocessSingle for
+// every packet of the slice, dpdk_worker_thread_utils.inc:67-135 + ppp.cc:69-156).
+//
+// Frame f carries the exponent of block f (f < B) in header dword 12 (pool
+// index BE16, exponent byte, zero byte) and the payload of block f - b.  The
+// wave of block k therefore writes:
+//  * frame k + b: header dwords 0-11 and the payload — one wave writes all
+//    of the frame but dword 12 (and dword 12 too once k + b >= B: those
+//    frames carry exponent 0);
+//  * dword 12 of frame k (k >= b), or the whole of extra-batch frame k
+//    (k < b: header with this exponent, zero payload).
+// One dword store instruction covers 4 frames: lane l < 48 writes dword
+// l % 12 of payload frame l / 12, lanes 48-51 write dword 12 of the 4
+// exponent frames.  Constant dwords are picked once per wave; the pool index
+// (PktId2PoolIndex) costs one 64-bit modulo per tile.
+__device__ __forceinline__ uint32_t pool_dword(const FrameArgs& a, uint32_t i, uint32_t exp_byte) {
+    const uint32_t pool = i < a.mop ? ((a.pool_start + i) & 0xffffu) : (((a.pool_start + (i - a.mop)) | 0x8000u) & 0xffffu);
+    return (pool >> 8) | ((pool & 0xffu) << 8) | ((exp_byte & 0xffu) << 16);
+}
+
+// Held to 8 waves per SIMD: left to itself hipcc gives it 106 SGPRs, which
+// caps it at 7; at 8 (a few SGPRs live in VGPR lanes, no scratch) the
+// 256 MiB bucket's frames take 4 % less time (profiles/r02c/ab_frames_occupancy.json).
+// The rx apply pass measured 1.6 % slower the same way and is left alone.
+// NTS: the payload words take non-temporal stores (frames in device memory
+// from the non-temporal threshold on).  Measured on cold frame sets (4
+// cycled, 256 MiB bucket, profiles/r04/ab_frames_nt.json): 98.1 -> 86.4 us;
+// non-temporal header dwords as well: 109.6 us (partial-line stores), so
+// headers keep the default policy.
+// I32: an INT32 job slice (DataType::INT32): no extra batch (a.b = 0), so
+// frame f carries block f; its payload is htonl of the block's words
+// (ppp.cc:158-190) and its exponent byte 0 — the same tile walk, no scale.
+// E: the slice's element policy.  A 16-bit slice (Elem16<H>) loads its tile
+// with one 8-byte access per lane per slice and widens it in registers; from
+// there on it is the FLOAT32 slice of the widened values, so its frames are
+// those of x.float() byte for byte.
+// The 16-bit instances keep the 8 waves wherever they reach them without
+// scratch, which is everywhere but P = 64 with local exponents (16 packets
+// per tile): held to 8 those spill 4 VGPRs, as the fp32 ones do; they are
+// given 7 instead and use no scratch.
+template <int P, class E, bool GLOBAL>
+constexpr int frames_min_waves() { return E::kBytes == 2 && P == 64 && !GLOBAL ? 7 : 8; }
+
+template <int P, class E, bool GLOBAL, bool NTS = false, bool I32 = false>
+__global__ __attribute__((amdgpu_waves_per_eu(frames_min_waves<P, E, GLOBAL>(), 8))) __launch_bounds__(kBlockThreads)
+void k_quantize_frames(FrameArgs a) {
+    __shared__ float lut[256];
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
+    const uint64_t padded = a.nblocks * P;
+    constexpr int kPk = kTileElems / P;                   // packets per tile
+    constexpr int kLanesPerPk = P / 4 < kWave ? P / 4 : kWave;
+    const int hd = lane % 12;                              // header dword of lanes 0..47
+    const int hj = lane < 48 ? lane / 12 : lane - 48;      // frame (of 4) of lanes 0..51
+    uint32_t hconst = a.hdr[0];
+#pragma unroll
+    for (int i = 1; i < 11; i++) hconst = hd == i ? a.hdr[i] : hconst;
+    const uint32_t m2 = 2u * a.mop;
+    QuantArgs<typename E::raw> qa;                         // reuse the K1 tile loader
+    qa.in = static_cast<const typename E::raw*>(a.in);
+    qa.numel = a.numel;
+    // As K1: the first tile's loads go out before the scale table is built.
+    uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index();
+    f4 v[kU];
+    if (t < a.ntiles) load_tile<E>(qa, t * kTileElems, lane, v);
+    if constexpr (!I32) build_lut(lut, a.W);
+    for (bool first = true; t < a.ntiles; t += nwaves, first = false) {
+        const uint64_t base = t * kTileElems;
+        const uint64_t pk0 = base / P;                     // first block of the tile
+        if (!first) load_tile<E>(qa, base, lane, v);       // later tiles (grid-stride)
+        int eloc[kU];
+        if constexpr (I32) {
+#pragma unroll
+            for (int u = 0; u < kU; u++) eloc[u] = 0;
+        } else {
+            tile_exponents<P>(v, eloc);
+        }
+        // exponent of packet j of the tile: slice j*P/256, lane (j*P/4) % 64
+        uint32_t ej[kPk];
+#pragma unroll
+        for (int j = 0; j < kPk; j++) {
+            const int u = (j * P) / 256;
+            ej[j] = 0;
+#pragma unroll
+            for (int uu = 0; uu < kU; uu++)
+                if (uu == u) ej[j] = (uint32_t)__builtin_amdgcn_readlane(eloc[uu], (j * kLanesPerPk) % kWave);
+        }
+        const uint32_t r = (uint32_t)((pk0 + a.pool_shift) % m2);   // pool slot of frame pk0
+        const bool extra = pk0 < a.b;                               // wave-uniform, first b / kPk tiles
+#pragma unroll
+        for (int j0 = 0; j0 < kPk; j0 += 4) {
+            const int j = j0 + hj;
+            if (lane < 48) {
+                if (j < kPk && pk0 + j < a.nblocks) {
+                    const uint64_t f = pk0 + j + a.b;
+                    *reinterpret_cast<uint32_t*>(a.frames + f * a.stride + 4 * hd) = hd == 11 ? (uint32_t)f : hconst;
+                }
+            } else if (lane < 52 && !extra) {
+                if (j < kPk && pk0 + j < a.nblocks) {
+                    uint32_t e = 0;
+#pragma unroll
+                    for (int jj = 0; jj < kPk; jj++) e = j == jj ? ej[jj] : e;
+                    *reinterpret_cast<uint32_t*>(a.frames + (pk0 + j) * a.stride + 48) = pool_dword(a, (r + (uint32_t)j) % m2, e);
+                }
+            }
+        }
+        if (__builtin_expect(pk0 + kPk + a.b > a.nblocks, 0)) {
+            // tail: payload frames at or past B carry exponent 0; their dword 12 is ours
+            if (lane < kPk && pk0 + lane < a.nblocks && pk0 + lane + a.b >= a.nblocks) {
+                const uint64_t f = pk0 + lane + a.b;
+                *reinterpret_cast<uint32_t*>(a.frames + f * a.stride + 48) =
+                    pool_dword(a, (uint32_t)((f + a.pool_shift) % m2), 0u);
+            }
+        }
+        if (__builtin_expect(extra, 0)) {
+            // extra-batch frames: header with this tile's exponent, zero payload; all ours
+#pragma unroll
+            for (int j = 0; j < kPk; j++) {
+                const uint64_t pk = pk0 + j;
+                if (pk >= a.nblocks) break;
+                if (pk < a.b) {
+                    write_frame_header(a, pk, lane, ej[j]);
+                    uint32_t* pl = reinterpret_cast<uint32_t*>(a.frames + pk * a.stride + 52);
+                    for (int i = lane; i < P / 4; i += kWave) *reinterpret_cast<u4a*>(pl + 4 * i) = u4a{0u, 0u, 0u, 0u};
+                } else if (lane == 0) {
+                    *reinterpret_cast<uint32_t*>(a.frames + pk * a.stride + 48) =
+                        pool_dword(a, (uint32_t)((pk + a.pool_shift) % m2), ej[j]);
+                }
+            }
+        }
+        // payloads
+#pragma unroll
+        for (int u = 0; u < kU; u++) {
+            const uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
+            if (idx >= padded) continue;
+            const uint64_t k = idx / P;
+            u4 q;
+            if constexpr (I32) {
+                // the words as loaded (whole-vector bit cast: hipcc's bit cast of one
+                // vector component returned component x for every component)
+                q = __builtin_bit_cast(u4, v[u]);
+            } else {
+                int e = eloc[u];
+                if constexpr (GLOBAL) e = a.gexp[k];
+                q = quantize4<false>(v[u], lut[(uint8_t)e], idx, 0);
+            }
+            uint32_t* dst = reinterpret_cast<uint32_t*>(a.frames + (k + a.b) * a.stride + 52) + (idx - k * P);
+            const u4a wq{bswap(q.x), bswap(q.y), bswap(q.z), bswap(q.w)};
+            if constexpr (NTS) SML_NT_STORE16_UNALIGNED(wq, reinterpret_cast<u4a*>(dst));
+            else *reinterpret_cast<u4a*>(dst) = wq;
+        }
+    }
+}
+
+// ------------------------------------------------- DPDK frames, receive side
+//
+// The rx bitmap of DpdkWorkerThread (dpdk_worker_thread.cc:316-342) becomes a
+// per-slice 64-bit state word per packet id: high half 0 = not received,
+// kRxDone = received in an earlier call, otherwise the claim tag of the frame
+// that won it in the current call (larger tag = earlier frame, so a 64-bit
+// atomicMax picks the first copy); low byte = that frame's exponent byte, so
+// the winner's exponent travels with the claim (PostprocessSingle's
+// scaling_factors_[pkt_id], ppp.cc:254-260) and needs no separate pass.
+constexpr uint32_t kRxDone = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t rx_tag(uint64_t f) { return 0xFFFFFFFEu - (uint32_t)f; }
+
+struct RxArgs {
+    const uint8_t* frames;
+    uint64_t nframes;
+    uint64_t stride;
+    uint64_t numel;
+    uint64_t nblocks;           // B
+    uint64_t b;                 // extra batch
+    unsigned long long* state;  // [B + b]
+    int8_t* exps;               // [B]
+    void* out;                  // the slice: E::raw elements (INT32: words stored as bits)
+    unsigned long long* counts; // {accepted, discarded} or nullptr
+    uint32_t W;
+    uint32_t xcd;           // xcd_block chunk (0 = plain order)
+    uint32_t job;               // (uint8_t)job_id
+};
+
+// Header dwords 10..12 of frame f: short_job_id = byte 43, pkt_id = bytes
+// 44-47 (host order), exponent = byte 50.
+struct RxHdr {
+    uint32_t pid;
+    uint32_t exp;
+    bool ok;                    // this job, pkt_id in range
+};
+
+typedef uint32_t u3a __attribute__((ext_vector_type(3), aligned(4)));
+
+__device__ __forceinline__ RxHdr rx_header(const RxArgs& a, uint64_t f) {
+    // one 12-byte load for dwords 10..12 (the compiler otherwise sinks the
+    // dword-12 load behind the job / range check: two round trips).  Default
+    // cache policy, not non-temporal: the 128-byte line it fetches also holds
+    // the first payload bytes (offset 52), which the apply pass reads next —
+    // kept in the caches, that line is not fetched from HBM a second time
+    // (cold frame sets: 94.7 -> 91.0 us per 256 MiB rx call,
+    // profiles/r05/ab_rx_claim_policy.json).
+    const u3a hv = *reinterpret_cast<const u3a*>(a.frames + f * a.stride + 40);
+    const uint32_t d10 = hv.x, d11 = hv.y, d12 = hv.z;
+    RxHdr r;
+    r.pid = d11;
+    r.exp = (d12 >> 16) & 0xffu;
+    r.ok = (d10 >> 24) == a.job && (uint64_t)d11 < a.nblocks + a.b;
+    return r;
+}
+
+// Pass 2: PostprocessSingle for every winning frame, walked in block order:
+// the wave of blocks k .. k + 1024/P - 1 reads state[k + b] (the claim tag of
+// the frame that won pkt_id k + b in this call, which names that frame) and
+// state[k] (low byte = exponent of block k, held by a winner of this call or
+// kRxDone), then gathers the winner's payload and writes out[k*P ..]
+// contiguously.  No header is read again; pkt_ids without a winner in this
+// call (not received, or received earlier) write nothing; the same pass then
+// retires the winners.
+// 16-B chunks per lane per tile (slices of 256 elements); a tile holds whole
+// packets, so never below P / 256.  2 against 4 on 4 cycled 256 MiB frame
+// sets: 97.63 -> 95.59 us per rx call (profiles/r04/ab_rx_slices.json), as
+// the plane kernels moved to 2-slice tiles.  A 16-bit output starts on the
+// same count.
+__host__ __device__ constexpr int rx_slices(int P) { return P / 256 > 2 ? P / 256 : 2; }
+
+__device__ __forceinline__ bool rx_winner(unsigned long long sw, uint64_t nframes, uint64_t& f) {
+    const uint32_t hi = (uint32_t)(sw >> 32);
+    f = 0xFFFFFFFEull - hi;                    // rx_tag inverse
+    return hi != 0u && hi != kRxDone && f < nframes;
+}
+
+// E: the output's element policy.  fp32 (ElemF32<true>) stores a whole
+// 16-byte vector where the address allows it; a 16-bit output (Elem16<H>)
+// narrows the four fp32 results and stores them with one 8-byte access at any
+// 2-byte alignment.  Either way a slice's partial tail goes element by element.
+template <int P, class E, bool NT = false>
+__global__ __launch_bounds__(kBlockThreads) void k_rx_apply(RxArgs a) {
+    __shared__ float lut[256];
+    // power-of-two W: the table holds exact reciprocals and dequantize multiplies
+    // (bit-equal to the IEEE division, rcp_scale_pow2); otherwise scales
+    const bool pow2 = (a.W & (a.W - 1)) == 0;
+    if (pow2) build_rcp_lut(lut, a.W);
+    else build_lut(lut, a.W);
+    constexpr int kRxU = rx_slices(P);
+    constexpr int kRxTileElems = kRxU * kWave * 4;
+    constexpr int kChunksPerFrame = P / 4;     // 16-B chunks per payload
+    constexpr int kBlocksPerTile = kRxTileElems / P;
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
+    const uint64_t ntiles = (a.nblocks + kBlocksPerTile - 1) / kBlocksPerTile;
+    for (uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index(); t < ntiles; t += nwaves) {
+        u4a w[kRxU];
+        bool ok[kRxU];
+        float s[kRxU];
+        uint64_t f[kRxU];
+        // The state words are read unconditionally (index clamped into the
+        // slice) so that all of them are in flight at once: per-slice guarded
+        // reads made hipcc wait for each one before issuing the next.
+        unsigned long long sw[kRxU], se[kRxU];
+        if constexpr (kChunksPerFrame >= kWave) {
+            // P >= 256: slice u of the tile lies in one block, so its state
+            // words are wave-uniform: scalar loads
+            const ConstU64* state = reinterpret_cast<const ConstU64*>(reinterpret_cast<uintptr_t>(a.state));
+#pragma unroll
+            for (int u = 0; u < kRxU; u++) {
+                const uint64_t k = t * kBlocksPerTile + (u * kWave) / kChunksPerFrame;
+                const uint64_t kc = k < a.nblocks ? k : a.nblocks - 1;
+                sw[u] = state[kc + a.b];
+                se[u] = state[kc];
+            }
+#pragma unroll
+            for (int u = 0; u < kRxU; u++) {
+                const uint64_t k = t * kBlocksPerTile + (u * kWave) / kChunksPerFrame;
+                ok[u] = rx_winner(sw[u], a.nframes, f[u]) && k < a.nblocks;
+                s[u] = lut[(uint32_t)se[u] & 0xffu];
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < kRxU; u++) {
+                const uint64_t k = t * kBlocksPerTile + (u * kWave + lane) / kChunksPerFrame;
+                const uint64_t kc = k < a.nblocks ? k : a.nblocks - 1;
+                sw[u] = a.state[kc + a.b];
+                se[u] = a.state[kc];
+            }
+#pragma unroll
+            for (int u = 0; u < kRxU; u++) {
+                const uint64_t k = t * kBlocksPerTile + (u * kWave + lane) / kChunksPerFrame;
+                ok[u] = rx_winner(sw[u], a.nframes, f[u]) && k < a.nblocks;
+                s[u] = lut[(uint32_t)se[u] & 0xffu];
+            }
+        }
+        // Non-temporal payload loads (25 % faster than default-policy loads for
+        // this stream, hbm_probe), issued unconditionally so they are all in
+        // flight together: a slice without a winner reads frame 0's (L2-hot)
+        // bytes instead and its words are zeroed.
+#pragma unroll
+        for (int u = 0; u < kRxU; u++)
+            w[u] = __builtin_nontemporal_load(reinterpret_cast<const u4a*>(
+                a.frames + (ok[u] ? f[u] : 0ull) * a.stride + 52 + 16ull * ((u * kWave + lane) % kChunksPerFrame)));
+#pragma unroll
+        for (int u = 0; u < kRxU; u++)
+            if (!ok[u]) w[u] = u4a{0u, 0u, 0u, 0u};
+        // Dequantize all slices first, unconditionally (a slice without a
+        // winner computes on zeros and is not stored), then store: with the
+        // first use of the loaded words inside per-slice conditional blocks,
+        // hipcc waited vmcnt(0) — on the previous slice's store too — before
+        // every slice.
+        f4 o[kRxU];
+#pragma unroll
+        for (int u = 0; u < kRxU; u++) {
+            if (pow2)
+                o[u] = mkf4((float)(int32_t)bswap(w[u].x) * s[u], (float)(int32_t)bswap(w[u].y) * s[u],
+                            (float)(int32_t)bswap(w[u].z) * s[u], (float)(int32_t)bswap(w[u].w) * s[u]);
+            else
+                o[u] = mkf4(dequantize1(bswap(w[u].x), s[u]), dequantize1(bswap(w[u].y), s[u]),
+                            dequantize1(bswap(w[u].z), s[u]), dequantize1(bswap(w[u].w), s[u]));
+        }
+#pragma unroll
+        for (int u = 0; u < kRxU; u++) {
+            if (!ok[u]) continue;
+            const uint64_t off = t * kRxTileElems + 4ull * (u * kWave + lane);
+            if (off >= a.numel) continue;
+            typename E::raw* p = static_cast<typename E::raw*>(a.out) + off;
+            // whole vectors: fp32 where the address is 16-byte aligned, a
+            // 16-bit type anywhere (its 8-byte access is declared 2-byte aligned)
+            if (a.numel - off >= 4 && (E::kBytes == 2 || ((uintptr_t)p & 15u) == 0)) E::template store4<NT>(p, o[u]);
+            else E::store4_guarded(p, o[u], 0, a.numel - off);
+        }
+        // The commit, folded in (it was a third launch): the lane that owns
+        // block k retires this call's winner of pkt_id k + b (state -> kRxDone,
+        // exponent byte kept), publishes exps[k] once pkt_id k is received, and
+        // for k < b retires the extra-batch pkt_id k too.  Every pkt_id's high
+        // half is read and written by exactly one wave (its own); other waves
+        // read only the low byte, which the retirement keeps.
+#pragma unroll
+        for (int u = 0; u < kRxU; u++) {
+            const uint64_t k = t * kBlocksPerTile + (u * kWave + lane) / kChunksPerFrame;
+            if (((u * kWave + lane) % kChunksPerFrame) != 0 || k >= a.nblocks) continue;
+            const uint32_t hw = (uint32_t)(sw[u] >> 32), he = (uint32_t)(se[u] >> 32);
+            if (hw != 0u && hw != kRxDone)
+                a.state[k + a.b] = ((unsigned long long)kRxDone << 32) | (sw[u] & 0xffull);
+            if (he != 0u) a.exps[k] = (int8_t)(se[u] & 0xffull);
+            if (k < a.b && he != 0u && he != kRxDone)
+                a.state[k] = ((unsigned long long)kRxDone << 32) | (se[u] & 0xffull);
+        }
+    }
+}
+
+// ------------------------------------------------------------ host side
+
+// The 16-bit instances' launches (sml_frames_half.hip), for the typed entry
+// points of sml_frames.hip, which have checked every argument and filled the
+// arguments: one launch each on `st`; f16: FLOAT16, else BFLOAT16.
+void launch_quantize_frames_h(const FrameArgs& a, bool f16, uint32_t P, bool global, bool nts, dim3 grid,
+                              hipStream_t st);
+void launch_rx_apply_h(const RxArgs& a, bool f16, uint32_t P, bool nt, dim3 grid, hipStream_t st);
+
+}  // namespace sml
+
+#endif  // SML_FRAME_KERNELS_H_

@@ -3,247 +3,12 @@
 // client_lib/src/backends/dpdk/dpdk_worker_thread_utils.inc:42-135) and the
 // receive side (DpdkWorkerThread's rx loop, dpdk_worker_thread.cc:300-345,
 // with PostprocessSingle per accepted frame), and their C-ABI entry points.
-#include "sml_host.h"
+// The kernels that touch the slice's typed buffer are the templates of
+// sml_frame_kernels.h, instantiated here for FLOAT32 and INT32; the FLOAT16 /
+// BFLOAT16 instances are sml_frames_half.hip's.
+#include "sml_frame_kernels.h"
 
 namespace sml {
-
-// ---------------------------------------------------------- DPDK frames
-
-struct FrameArgs {
-    const float* in;
-    uint64_t numel;
-    uint64_t nblocks;       // B
-    uint64_t ntiles;        // ceil(B*P / 1024)
-    uint64_t b;             // extra-batch size = min(batch_max, B)
-    const int8_t* gexp;     // global exponents or nullptr
-    uint8_t* frames;        // B + b frames, 4-byte aligned
-    uint64_t stride;        // bytes between frames, multiple of 4
-    uint32_t W;
-    uint32_t xcd;           // xcd_block chunk (0 = plain order)
-    uint32_t pool_start, pool_shift, mop;
-    uint32_t hdr[11];       // frame bytes 0..43: Eth, IPv4, UDP, job_type_size, short_job_id
-};
-
-// PktId2PoolIndex, dpdk_worker_thread_utils.inc:42-52.
-__device__ __forceinline__ uint32_t pool_index(uint64_t p, const FrameArgs& a) {
-    const uint32_t i = (uint32_t)((p + a.pool_shift) % (2ull * a.mop));
-    return i < a.mop ? ((a.pool_start + i) & 0xffffu) : (((a.pool_start + (i - a.mop)) | 0x8000u) & 0xffffu);
-}
-
-// Lanes 0..12 write the 52 header bytes of frame p (one dword each):
-// dwords 0-10 constant, 11 = pkt_id (host order), 12 = pool index (BE16),
-// exponent byte, zero byte.  (Extra-batch frames; the bulk of the headers is
-// written lane-parallel by k_quantize_frames.)
-__device__ __forceinline__ void write_frame_header(const FrameArgs& a, uint64_t p, int lane, uint32_t exp_byte) {
-    if (lane > 12) return;
-    uint32_t dw = a.hdr[0];
-#pragma unroll
-    for (int i = 1; i < 11; i++) dw = lane == i ? a.hdr[i] : dw;
-    if (lane == 11) dw = (uint32_t)p;
-    if (lane == 12) {
-        const uint32_t pool = pool_index(p, a);
-        dw = (pool >> 8) | ((pool & 0xffu) << 8) | ((exp_byte & 0xffu) << 16);
-    }
-    *reinterpret_cast<uint32_t*>(a.frames + p * a.stride + 4 * lane) = dw;
-}
-
-// Fused quantize + pack into DPDK frames (BuildPacket + PreprocessSingle for
-// every packet of the slice, dpdk_worker_thread_utils.inc:67-135 + ppp.cc:69-156).
-//
-// Frame f carries the exponent of block f (f < B) in header dword 12 (pool
-// index BE16, exponent byte, zero byte) and the payload of block f - b.  The
-// wave of block k therefore writes:
-//  * frame k + b: header dwords 0-11 and the payload — one wave writes all
-//    of the frame but dword 12 (and dword 12 too once k + b >= B: those
-//    frames carry exponent 0);
-//  * dword 12 of frame k (k >= b), or the whole of extra-batch frame k
-//    (k < b: header with this exponent, zero payload).
-// One dword store instruction covers 4 frames: lane l < 48 writes dword
-// l % 12 of payload frame l / 12, lanes 48-51 write dword 12 of the 4
-// exponent frames.  Constant dwords are picked once per wave; the pool index
-// (PktId2PoolIndex) costs one 64-bit modulo per tile.
-__device__ __forceinline__ uint32_t pool_dword(const FrameArgs& a, uint32_t i, uint32_t exp_byte) {
-    const uint32_t pool = i < a.mop ? ((a.pool_start + i) & 0xffffu) : (((a.pool_start + (i - a.mop)) | 0x8000u) & 0xffffu);
-    return (pool >> 8) | ((pool & 0xffu) << 8) | ((exp_byte & 0xffu) << 16);
-}
-
-// Held to 8 waves per SIMD: left to itself hipcc gives it 106 SGPRs, which
-// caps it at 7; at 8 (a few SGPRs live in VGPR lanes, no scratch) the
-// 256 MiB bucket's frames take 4 % less time (profiles/r02c/ab_frames_occupancy.json).
-// The rx apply pass measured 1.6 % slower the same way and is left alone.
-// NTS: the payload words take non-temporal stores (frames in device memory
-// from the non-temporal threshold on).  Measured on cold frame sets (4
-// cycled, 256 MiB bucket, profiles/r04/ab_frames_nt.json): 98.1 -> 86.4 us;
-// non-temporal header dwords as well: 109.6 us (partial-line stores), so
-// headers keep the default policy.
-// I32: an INT32 job slice (DataType::INT32): no extra batch (a.b = 0), so
-// frame f carries block f; its payload is htonl of the block's words
-// (ppp.cc:158-190) and its exponent byte 0 — the same tile walk, no scale.
-template <int P, bool ALIGNED, bool GLOBAL, bool NTS = false, bool I32 = false>
-__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(kBlockThreads)
-void k_quantize_frames(FrameArgs a) {
-    __shared__ float lut[256];
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
-    const uint64_t padded = a.nblocks * P;
-    constexpr int kPk = kTileElems / P;                   // packets per tile
-    constexpr int kLanesPerPk = P / 4 < kWave ? P / 4 : kWave;
-    const int hd = lane % 12;                              // header dword of lanes 0..47
-    const int hj = lane < 48 ? lane / 12 : lane - 48;      // frame (of 4) of lanes 0..51
-    uint32_t hconst = a.hdr[0];
-#pragma unroll
-    for (int i = 1; i < 11; i++) hconst = hd == i ? a.hdr[i] : hconst;
-    const uint32_t m2 = 2u * a.mop;
-    QuantArgs<float> qa;                                   // reuse the K1 tile loader
-    qa.in = a.in;
-    qa.numel = a.numel;
-    // As K1: the first tile's loads go out before the scale table is built.
-    uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index();
-    f4 v[kU];
-    if (t < a.ntiles) load_tile<ElemF32<ALIGNED>>(qa, t * kTileElems, lane, v);
-    if constexpr (!I32) build_lut(lut, a.W);
-    for (bool first = true; t < a.ntiles; t += nwaves, first = false) {
-        const uint64_t base = t * kTileElems;
-        const uint64_t pk0 = base / P;                     // first block of the tile
-        if (!first) load_tile<ElemF32<ALIGNED>>(qa, base, lane, v); // later tiles (grid-stride)
-        int eloc[kU];
-        if constexpr (I32) {
-#pragma unroll
-            for (int u = 0; u < kU; u++) eloc[u] = 0;
-        } else {
-            tile_exponents<P>(v, eloc);
-        }
-        // exponent of packet j of the tile: slice j*P/256, lane (j*P/4) % 64
-        uint32_t ej[kPk];
-#pragma unroll
-        for (int j = 0; j < kPk; j++) {
-            const int u = (j * P) / 256;
-            ej[j] = 0;
-#pragma unroll
-            for (int uu = 0; uu < kU; uu++)
-                if (uu == u) ej[j] = (uint32_t)__builtin_amdgcn_readlane(eloc[uu], (j * kLanesPerPk) % kWave);
-        }
-        const uint32_t r = (uint32_t)((pk0 + a.pool_shift) % m2);   // pool slot of frame pk0
-        const bool extra = pk0 < a.b;                               // wave-uniform, first b / kPk tiles
-#pragma unroll
-        for (int j0 = 0; j0 < kPk; j0 += 4) {
-            const int j = j0 + hj;
-            if (lane < 48) {
-                if (j < kPk && pk0 + j < a.nblocks) {
-                    const uint64_t f = pk0 + j + a.b;
-                    *reinterpret_cast<uint32_t*>(a.frames + f * a.stride + 4 * hd) = hd == 11 ? (uint32_t)f : hconst;
-                }
-            } else if (lane < 52 && !extra) {
-                if (j < kPk && pk0 + j < a.nblocks) {
-                    uint32_t e = 0;
-#pragma unroll
-                    for (int jj = 0; jj < kPk; jj++) e = j == jj ? ej[jj] : e;
-                    *reinterpret_cast<uint32_t*>(a.frames + (pk0 + j) * a.stride + 48) = pool_dword(a, (r + (uint32_t)j) % m2, e);
-                }
-            }
-        }
-        if (__builtin_expect(pk0 + kPk + a.b > a.nblocks, 0)) {
-            // tail: payload frames at or past B carry exponent 0; their dword 12 is ours
-            if (lane < kPk && pk0 + lane < a.nblocks && pk0 + lane + a.b >= a.nblocks) {
-                const uint64_t f = pk0 + lane + a.b;
-                *reinterpret_cast<uint32_t*>(a.frames + f * a.stride + 48) =
-                    pool_dword(a, (uint32_t)((f + a.pool_shift) % m2), 0u);
-            }
-        }
-        if (__builtin_expect(extra, 0)) {
-            // extra-batch frames: header with this tile's exponent, zero payload; all ours
-#pragma unroll
-            for (int j = 0; j < kPk; j++) {
-                const uint64_t pk = pk0 + j;
-                if (pk >= a.nblocks) break;
-                if (pk < a.b) {
-                    write_frame_header(a, pk, lane, ej[j]);
-                    uint32_t* pl = reinterpret_cast<uint32_t*>(a.frames + pk * a.stride + 52);
-                    for (int i = lane; i < P / 4; i += kWave) *reinterpret_cast<u4a*>(pl + 4 * i) = u4a{0u, 0u, 0u, 0u};
-                } else if (lane == 0) {
-                    *reinterpret_cast<uint32_t*>(a.frames + pk * a.stride + 48) =
-                        pool_dword(a, (uint32_t)((pk + a.pool_shift) % m2), ej[j]);
-                }
-            }
-        }
-        // payloads
-#pragma unroll
-        for (int u = 0; u < kU; u++) {
-            const uint64_t idx = base + (uint64_t)(u * kWave + lane) * 4;
-            if (idx >= padded) continue;
-            const uint64_t k = idx / P;
-            u4 q;
-            if constexpr (I32) {
-                // the words as loaded (whole-vector bit cast: hipcc's bit cast of one
-                // vector component returned component x for every component)
-                q = __builtin_bit_cast(u4, v[u]);
-            } else {
-                int e = eloc[u];
-                if constexpr (GLOBAL) e = a.gexp[k];
-                q = quantize4<false>(v[u], lut[(uint8_t)e], idx, 0);
-            }
-            uint32_t* dst = reinterpret_cast<uint32_t*>(a.frames + (k + a.b) * a.stride + 52) + (idx - k * P);
-            const u4a wq{bswap(q.x), bswap(q.y), bswap(q.z), bswap(q.w)};
-            if constexpr (NTS) SML_NT_STORE16_UNALIGNED(wq, reinterpret_cast<u4a*>(dst));
-            else *reinterpret_cast<u4a*>(dst) = wq;
-        }
-    }
-}
-
-// ------------------------------------------------- DPDK frames, receive side
-//
-// The rx bitmap of DpdkWorkerThread (dpdk_worker_thread.cc:316-342) becomes a
-// per-slice 64-bit state word per packet id: high half 0 = not received,
-// kRxDone = received in an earlier call, otherwise the claim tag of the frame
-// that won it in the current call (larger tag = earlier frame, so a 64-bit
-// atomicMax picks the first copy); low byte = that frame's exponent byte, so
-// the winner's exponent travels with the claim (PostprocessSingle's
-// scaling_factors_[pkt_id], ppp.cc:254-260) and needs no separate pass.
-constexpr uint32_t kRxDone = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t rx_tag(uint64_t f) { return 0xFFFFFFFEu - (uint32_t)f; }
-
-struct RxArgs {
-    const uint8_t* frames;
-    uint64_t nframes;
-    uint64_t stride;
-    uint64_t numel;
-    uint64_t nblocks;           // B
-    uint64_t b;                 // extra batch
-    unsigned long long* state;  // [B + b]
-    int8_t* exps;               // [B]
-    float* out;
-    unsigned long long* counts; // {accepted, discarded} or nullptr
-    uint32_t W;
-    uint32_t xcd;           // xcd_block chunk (0 = plain order)
-    uint32_t job;               // (uint8_t)job_id
-};
-
-// Header dwords 10..12 of frame f: short_job_id = byte 43, pkt_id = bytes
-// 44-47 (host order), exponent = byte 50.
-struct RxHdr {
-    uint32_t pid;
-    uint32_t exp;
-    bool ok;                    // this job, pkt_id in range
-};
-
-typedef uint32_t u3a __attribute__((ext_vector_type(3), aligned(4)));
-
-__device__ __forceinline__ RxHdr rx_header(const RxArgs& a, uint64_t f) {
-    // one 12-byte load for dwords 10..12 (the compiler otherwise sinks the
-    // dword-12 load behind the job / range check: two round trips).  Default
-    // cache policy, not non-temporal: the 128-byte line it fetches also holds
-    // the first payload bytes (offset 52), which the apply pass reads next —
-    // kept in the caches, that line is not fetched from HBM a second time
-    // (cold frame sets: 94.7 -> 91.0 us per 256 MiB rx call,
-    // profiles/r05/ab_rx_claim_policy.json).
-    const u3a hv = *reinterpret_cast<const u3a*>(a.frames + f * a.stride + 40);
-    const uint32_t d10 = hv.x, d11 = hv.y, d12 = hv.z;
-    RxHdr r;
-    r.pid = d11;
-    r.exp = (d12 >> 16) & 0xffu;
-    r.ok = (d10 >> 24) == a.job && (uint64_t)d11 < a.nblocks + a.b;
-    return r;
-}
 
 // Pass 1, thread per frame: frames of another job, out-of-range or already
 // received pkt_ids are discarded; the others claim their pkt_id.  Counting:
@@ -278,140 +43,6 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_claim(RxArgs a) {
         acc -= disc;                                                 // mod 2^64
         if (acc) atomicAdd(a.counts + 0, acc);
         if (disc) atomicAdd(a.counts + 1, (unsigned long long)disc);
-    }
-}
-
-// Pass 2: PostprocessSingle for every winning frame, walked in block order:
-// the wave of blocks k .. k + 1024/P - 1 reads state[k + b] (the claim tag of
-// the frame that won pkt_id k + b in this call, which names that frame) and
-// state[k] (low byte = exponent of block k, held by a winner of this call or
-// kRxDone), then gathers the winner's payload and writes out[k*P ..]
-// contiguously.  No header is read again; pkt_ids without a winner in this
-// call (not received, or received earlier) write nothing; the same pass then
-// retires the winners.
-// 16-B chunks per lane per tile (slices of 256 elements); a tile holds whole
-// packets, so never below P / 256.  2 against 4 on 4 cycled 256 MiB frame
-// sets: 97.63 -> 95.59 us per rx call (profiles/r04/ab_rx_slices.json), as
-// the plane kernels moved to 2-slice tiles.
-__host__ __device__ constexpr int rx_slices(int P) { return P / 256 > 2 ? P / 256 : 2; }
-
-__device__ __forceinline__ bool rx_winner(unsigned long long sw, uint64_t nframes, uint64_t& f) {
-    const uint32_t hi = (uint32_t)(sw >> 32);
-    f = 0xFFFFFFFEull - hi;                    // rx_tag inverse
-    return hi != 0u && hi != kRxDone && f < nframes;
-}
-
-template <int P, bool NT = false>
-__global__ __launch_bounds__(kBlockThreads) void k_rx_apply(RxArgs a) {
-    __shared__ float lut[256];
-    // power-of-two W: the table holds exact reciprocals and dequantize multiplies
-    // (bit-equal to the IEEE division, rcp_scale_pow2); otherwise scales
-    const bool pow2 = (a.W & (a.W - 1)) == 0;
-    if (pow2) build_rcp_lut(lut, a.W);
-    else build_lut(lut, a.W);
-    constexpr int kRxU = rx_slices(P);
-    constexpr int kRxTileElems = kRxU * kWave * 4;
-    constexpr int kChunksPerFrame = P / 4;     // 16-B chunks per payload
-    constexpr int kBlocksPerTile = kRxTileElems / P;
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
-    const uint64_t ntiles = (a.nblocks + kBlocksPerTile - 1) / kBlocksPerTile;
-    for (uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index(); t < ntiles; t += nwaves) {
-        u4a w[kRxU];
-        bool ok[kRxU];
-        float s[kRxU];
-        uint64_t f[kRxU];
-        // The state words are read unconditionally (index clamped into the
-        // slice) so that all of them are in flight at once: per-slice guarded
-        // reads made hipcc wait for each one before issuing the next.
-        unsigned long long sw[kRxU], se[kRxU];
-        if constexpr (kChunksPerFrame >= kWave) {
-            // P >= 256: slice u of the tile lies in one block, so its state
-            // words are wave-uniform: scalar loads
-            const ConstU64* state = reinterpret_cast<const ConstU64*>(reinterpret_cast<uintptr_t>(a.state));
-#pragma unroll
-            for (int u = 0; u < kRxU; u++) {
-                const uint64_t k = t * kBlocksPerTile + (u * kWave) / kChunksPerFrame;
-                const uint64_t kc = k < a.nblocks ? k : a.nblocks - 1;
-                sw[u] = state[kc + a.b];
-                se[u] = state[kc];
-            }
-#pragma unroll
-            for (int u = 0; u < kRxU; u++) {
-                const uint64_t k = t * kBlocksPerTile + (u * kWave) / kChunksPerFrame;
-                ok[u] = rx_winner(sw[u], a.nframes, f[u]) && k < a.nblocks;
-                s[u] = lut[(uint32_t)se[u] & 0xffu];
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < kRxU; u++) {
-                const uint64_t k = t * kBlocksPerTile + (u * kWave + lane) / kChunksPerFrame;
-                const uint64_t kc = k < a.nblocks ? k : a.nblocks - 1;
-                sw[u] = a.state[kc + a.b];
-                se[u] = a.state[kc];
-            }
-#pragma unroll
-            for (int u = 0; u < kRxU; u++) {
-                const uint64_t k = t * kBlocksPerTile + (u * kWave + lane) / kChunksPerFrame;
-                ok[u] = rx_winner(sw[u], a.nframes, f[u]) && k < a.nblocks;
-                s[u] = lut[(uint32_t)se[u] & 0xffu];
-            }
-        }
-        // Non-temporal payload loads (25 % faster than default-policy loads for
-        // this stream, hbm_probe), issued unconditionally so they are all in
-        // flight together: a slice without a winner reads frame 0's (L2-hot)
-        // bytes instead and its words are zeroed.
-#pragma unroll
-        for (int u = 0; u < kRxU; u++)
-            w[u] = __builtin_nontemporal_load(reinterpret_cast<const u4a*>(
-                a.frames + (ok[u] ? f[u] : 0ull) * a.stride + 52 + 16ull * ((u * kWave + lane) % kChunksPerFrame)));
-#pragma unroll
-        for (int u = 0; u < kRxU; u++)
-            if (!ok[u]) w[u] = u4a{0u, 0u, 0u, 0u};
-        // Dequantize all slices first, unconditionally (a slice without a
-        // winner computes on zeros and is not stored), then store: with the
-        // first use of the loaded words inside per-slice conditional blocks,
-        // hipcc waited vmcnt(0) — on the previous slice's store too — before
-        // every slice.
-        f4 o[kRxU];
-#pragma unroll
-        for (int u = 0; u < kRxU; u++) {
-            if (pow2)
-                o[u] = mkf4((float)(int32_t)bswap(w[u].x) * s[u], (float)(int32_t)bswap(w[u].y) * s[u],
-                            (float)(int32_t)bswap(w[u].z) * s[u], (float)(int32_t)bswap(w[u].w) * s[u]);
-            else
-                o[u] = mkf4(dequantize1(bswap(w[u].x), s[u]), dequantize1(bswap(w[u].y), s[u]),
-                            dequantize1(bswap(w[u].z), s[u]), dequantize1(bswap(w[u].w), s[u]));
-        }
-#pragma unroll
-        for (int u = 0; u < kRxU; u++) {
-            if (!ok[u]) continue;
-            const uint64_t off = t * kRxTileElems + 4ull * (u * kWave + lane);
-            if (off >= a.numel) continue;
-            float* p = a.out + off;
-            if (a.numel - off >= 4 && ((uintptr_t)p & 15u) == 0) {
-                if constexpr (NT) SML_NT_STORE16(o[u], reinterpret_cast<f4*>(p));
-                else *reinterpret_cast<f4*>(p) = o[u];
-            }
-            else store4_guarded(p, o[u], 0, a.numel - off);
-        }
-        // The commit, folded in (it was a third launch): the lane that owns
-        // block k retires this call's winner of pkt_id k + b (state -> kRxDone,
-        // exponent byte kept), publishes exps[k] once pkt_id k is received, and
-        // for k < b retires the extra-batch pkt_id k too.  Every pkt_id's high
-        // half is read and written by exactly one wave (its own); other waves
-        // read only the low byte, which the retirement keeps.
-#pragma unroll
-        for (int u = 0; u < kRxU; u++) {
-            const uint64_t k = t * kBlocksPerTile + (u * kWave + lane) / kChunksPerFrame;
-            if (((u * kWave + lane) % kChunksPerFrame) != 0 || k >= a.nblocks) continue;
-            const uint32_t hw = (uint32_t)(sw[u] >> 32), he = (uint32_t)(se[u] >> 32);
-            if (hw != 0u && hw != kRxDone)
-                a.state[k + a.b] = ((unsigned long long)kRxDone << 32) | (sw[u] & 0xffull);
-            if (he != 0u) a.exps[k] = (int8_t)(se[u] & 0xffull);
-            if (k < a.b && he != 0u && he != kRxDone)
-                a.state[k] = ((unsigned long long)kRxDone << 32) | (se[u] & 0xffull);
-        }
     }
 }
 
@@ -555,7 +186,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_int32(RxArgs a) {
             if (off >= a.numel) continue;
             const u4a& w = cur.w[u];
             const f4 o = __builtin_bit_cast(f4, mku4(bswap(w.x), bswap(w.y), bswap(w.z), bswap(w.w)));
-            float* p = a.out + off;
+            float* p = static_cast<float*>(a.out) + off;
             if (a.numel - off >= 4 && ((uintptr_t)p & 15u) == 0) {
                 // a wave's F frames land anywhere in the output (their pkt_ids),
                 // so not SML_NT_STORE16: its buffer resource spans +-1 GiB
@@ -749,17 +380,18 @@ static RxArgs rx_args(const void* frames, uint64_t num_frames, uint64_t stride, 
     return a;
 }
 
-}  // namespace sml
-
-extern "C" {
-
-sml_status_t sml_quantize_pack_frames(const float* d_in, uint64_t numel, uint32_t P, uint16_t W,
-                                      const int8_t* d_global_exps, uint32_t batch_max,
-                                      const sml_frame_params* prm, void* frames, uint64_t stride, void* stream) {
+// The transmit side of a float slice of any type (the two entry points
+// below): d_in holds FLOAT32 elements (4-byte aligned) or, through the typed
+// entry point, FLOAT16 / BFLOAT16 ones (2-byte aligned).  Every check comes
+// before the launch.
+static sml_status_t quantize_frames(const void* d_in, sml_data_type_t dt, uint64_t numel, uint32_t P, uint16_t W,
+                                    const int8_t* d_global_exps, uint32_t batch_max, const sml_frame_params* prm,
+                                    void* frames, uint64_t stride, void* stream) {
     if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
     if (W == 0 || !prm || batch_max == 0) return SML_ERR_INVALID_ARG;
     if (numel == 0) return SML_OK;
-    if (!d_in || !aligned4(d_in)) return SML_ERR_INVALID_ARG;
+    const uintptr_t align = dt == SML_FLOAT32 ? 3u : 1u;
+    if (!d_in || ((uintptr_t)d_in & align)) return SML_ERR_INVALID_ARG;
     if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
     FrameArgs a;
     const uint64_t B = sml_num_blocks(numel, P);
@@ -768,49 +400,35 @@ sml_status_t sml_quantize_pack_frames(const float* d_in, uint64_t numel, uint32_
     a.gexp = d_global_exps;
     dim3 grid(grid_for_tiles(a.ntiles));
     hipStream_t st = (hipStream_t)stream;
-    const bool al = aligned16(d_in);
     const bool nts = frames_nt(frames, (a.nblocks + a.b) * stride);
+    if (dt != SML_FLOAT32) {
+        launch_quantize_frames_h(a, dt == SML_FLOAT16, P, d_global_exps != nullptr, nts, grid, st);
+        return launch_check();
+    }
+    const bool al = aligned16(d_in);
     dispatch_packet(P, [&](auto Pc) {
         dispatch_bools([&](auto AL, auto GLOBAL, auto NTS) {
-            k_quantize_frames<Pc(), AL(), GLOBAL(), NTS(), false><<<grid, kBlockThreads, 0, st>>>(a);
+            k_quantize_frames<Pc(), ElemF32<AL()>, GLOBAL(), NTS(), false><<<grid, kBlockThreads, 0, st>>>(a);
         }, al, d_global_exps != nullptr, nts);
     });
     return launch_check();
 }
 
-sml_status_t sml_pack_frames_int32(const int32_t* d_in, uint64_t numel, uint32_t P, const sml_frame_params* prm,
-                                   void* frames, uint64_t stride, void* stream) {
-    if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
-    if (!prm) return SML_ERR_INVALID_ARG;
-    if (numel == 0) return SML_OK;
-    if (!d_in || !aligned4(d_in)) return SML_ERR_INVALID_ARG;
-    if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
-    FrameArgs a;
-    frame_args(prm, numel, P, 1, 0, frames, stride, a);       // INT32: no extra batch
-    a.in = reinterpret_cast<const float*>(d_in);              // words moved as bits
-    dim3 grid(grid_for_tiles(a.ntiles));
-    hipStream_t st = (hipStream_t)stream;
-    const bool nts = frames_nt(frames, a.nblocks * stride);
-    dispatch_packet(P, [&](auto Pc) {
-        dispatch_bools([&](auto AL, auto NTS) {
-            // I32 exists only without global exponents: it has no scale
-            k_quantize_frames<Pc(), AL(), false, NTS(), true><<<grid, kBlockThreads, 0, st>>>(a);
-        }, aligned16(d_in), nts);
-    });
-    return launch_check();
-}
-
-sml_status_t sml_dequantize_frames(const void* frames, uint64_t num_frames, uint64_t stride,
-                                   uint64_t numel, uint32_t P, uint16_t W, uint32_t batch_max,
-                                   uint64_t job_id, int8_t* d_exps, uint64_t* d_state, float* d_out,
-                                   uint64_t* d_counts, void* stream) {
+// The receive side likewise: the claim pass sees no element; the apply pass
+// writes d_out as FLOAT32 (4-byte aligned) or as a 16-bit type (2-byte
+// aligned), with the store policy chosen by the output's bytes.
+static sml_status_t dequantize_frames(const void* frames, uint64_t num_frames, uint64_t stride, uint64_t numel,
+                                      uint32_t P, uint16_t W, uint32_t batch_max, uint64_t job_id, int8_t* d_exps,
+                                      uint64_t* d_state, void* d_out, sml_data_type_t dt, uint64_t* d_counts,
+                                      void* stream) {
     if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
     if (W == 0 || batch_max == 0) return SML_ERR_INVALID_ARG;
     if (num_frames == 0) return SML_OK;
     if (num_frames >= 0xFFFFFFFEull) return SML_ERR_UNSUPPORTED;
     if (!d_state || (numel && (!d_exps || !d_out))) return SML_ERR_INVALID_ARG;
     if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
-    if (!aligned4(d_out)) return SML_ERR_ALIGNMENT;
+    const uint64_t elem = dt == SML_FLOAT32 ? 4 : 2;
+    if ((uintptr_t)d_out & (elem - 1)) return SML_ERR_ALIGNMENT;
     if (((uintptr_t)d_state & 7u) || (d_counts && ((uintptr_t)d_counts & 7u))) return SML_ERR_ALIGNMENT;
     RxArgs a = rx_args(frames, num_frames, stride, numel, P, job_id, d_state, d_counts);
     const uint32_t U = (uint32_t)rx_slices((int)P);
@@ -826,12 +444,76 @@ sml_status_t sml_dequantize_frames(const void* frames, uint64_t num_frames, uint
     if (ntiles) {
         const dim3 grid(grid_for_tiles(ntiles));
         // the output takes non-temporal stores from the threshold on, as K4's
-        dispatch_packet(P, [&](auto Pc) {
-            dispatch_bools([&](auto NT) { k_rx_apply<Pc(), NT()><<<grid, kBlockThreads, 0, st>>>(a); },
-                           nt_from(4 * numel));
-        });
+        const bool nt = nt_from(elem * numel);
+        if (dt != SML_FLOAT32) {
+            launch_rx_apply_h(a, dt == SML_FLOAT16, P, nt, grid, st);
+        } else {
+            dispatch_packet(P, [&](auto Pc) {
+                dispatch_bools([&](auto NT) { k_rx_apply<Pc(), ElemF32<true>, NT()><<<grid, kBlockThreads, 0, st>>>(a); },
+                               nt);
+            });
+        }
     }
     return launch_check();
+}
+
+}  // namespace sml
+
+extern "C" {
+
+sml_status_t sml_quantize_pack_frames(const float* d_in, uint64_t numel, uint32_t P, uint16_t W,
+                                      const int8_t* d_global_exps, uint32_t batch_max,
+                                      const sml_frame_params* prm, void* frames, uint64_t stride, void* stream) {
+    return quantize_frames(d_in, SML_FLOAT32, numel, P, W, d_global_exps, batch_max, prm, frames, stride, stream);
+}
+
+sml_status_t sml_quantize_pack_frames_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel, uint32_t P,
+                                            uint16_t W, const int8_t* d_global_exps, uint32_t batch_max,
+                                            const sml_frame_params* prm, void* frames, uint64_t stride,
+                                            void* stream) {
+    if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
+    if (data_type != SML_FLOAT32 && !is_half(data_type)) return SML_ERR_UNSUPPORTED;
+    return quantize_frames(d_in, data_type, numel, P, W, d_global_exps, batch_max, prm, frames, stride, stream);
+}
+
+sml_status_t sml_pack_frames_int32(const int32_t* d_in, uint64_t numel, uint32_t P, const sml_frame_params* prm,
+                                   void* frames, uint64_t stride, void* stream) {
+    if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
+    if (!prm) return SML_ERR_INVALID_ARG;
+    if (numel == 0) return SML_OK;
+    if (!d_in || !aligned4(d_in)) return SML_ERR_INVALID_ARG;
+    if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
+    FrameArgs a;
+    frame_args(prm, numel, P, 1, 0, frames, stride, a);       // INT32: no extra batch
+    a.in = d_in;                                              // words moved as bits
+    dim3 grid(grid_for_tiles(a.ntiles));
+    hipStream_t st = (hipStream_t)stream;
+    const bool nts = frames_nt(frames, a.nblocks * stride);
+    dispatch_packet(P, [&](auto Pc) {
+        dispatch_bools([&](auto AL, auto NTS) {
+            // I32 exists only without global exponents: it has no scale
+            k_quantize_frames<Pc(), ElemF32<AL()>, false, NTS(), true><<<grid, kBlockThreads, 0, st>>>(a);
+        }, aligned16(d_in), nts);
+    });
+    return launch_check();
+}
+
+sml_status_t sml_dequantize_frames(const void* frames, uint64_t num_frames, uint64_t stride,
+                                   uint64_t numel, uint32_t P, uint16_t W, uint32_t batch_max,
+                                   uint64_t job_id, int8_t* d_exps, uint64_t* d_state, float* d_out,
+                                   uint64_t* d_counts, void* stream) {
+    return dequantize_frames(frames, num_frames, stride, numel, P, W, batch_max, job_id, d_exps, d_state, d_out,
+                             SML_FLOAT32, d_counts, stream);
+}
+
+sml_status_t sml_dequantize_frames_typed(const void* frames, uint64_t num_frames, uint64_t stride, uint64_t numel,
+                                         uint32_t P, uint16_t W, uint32_t batch_max, uint64_t job_id, int8_t* d_exps,
+                                         uint64_t* d_state, void* d_out, sml_data_type_t data_type,
+                                         uint64_t* d_counts, void* stream) {
+    if (!valid_packet(P)) return SML_ERR_UNSUPPORTED;
+    if (data_type != SML_FLOAT32 && !is_half(data_type)) return SML_ERR_UNSUPPORTED;
+    return dequantize_frames(frames, num_frames, stride, numel, P, W, batch_max, job_id, d_exps, d_state, d_out,
+                             data_type, d_counts, stream);
 }
 
 sml_status_t sml_unpack_frames_int32(const void* frames, uint64_t num_frames, uint64_t stride, uint64_t numel,
@@ -848,7 +530,7 @@ sml_status_t sml_unpack_frames_int32(const void* frames, uint64_t num_frames, ui
     a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
     a.b = 0;                                                  // INT32: no extra batch
     a.exps = nullptr;
-    a.out = reinterpret_cast<float*>(d_out);                  // words stored as bits
+    a.out = d_out;                                            // words stored as bits
     a.W = 1;
     hipStream_t st = (hipStream_t)stream;
     const uint64_t frames_per_tile = (uint64_t)rx_int32_slices((int)P) * kWave * 4 / P;

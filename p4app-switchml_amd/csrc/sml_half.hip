@@ -36,8 +36,6 @@ constexpr int kHU = 4;
 template <bool F16>
 using ElemHalf = Elem16<F16 ? kHalfF16 : kHalfBF16>;
 
-inline bool is_half(sml_data_type_t dt) { return dt == SML_FLOAT16 || dt == SML_BFLOAT16; }
-
 static sml_status_t quantize_common_h(const void* d_in, sml_data_type_t dt, uint64_t numel, uint32_t P, uint16_t W,
                                       const int8_t* d_gexp, int32_t* d_payload, int8_t* d_exps_out, uint32_t flags,
                                       void* stream) {

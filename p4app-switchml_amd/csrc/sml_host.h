@@ -35,6 +35,9 @@ inline bool valid_packet(uint32_t P) {
     return P == 64 || P == 128 || P == 256 || P == 512 || P == 1024;
 }
 
+// The 16-bit float types of the sml_*_typed entry points.
+inline bool is_half(sml_data_type_t dt) { return dt == SML_FLOAT16 || dt == SML_BFLOAT16; }
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 

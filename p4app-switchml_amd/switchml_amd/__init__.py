@@ -146,6 +146,11 @@ def lib():
     L.sml_set_xcd_chunk.argtypes = [u32]
     L.sml_dequantize_frames.restype = i32
     L.sml_dequantize_frames.argtypes = [vp, u64, u64, u64, u32, u16, u32, u64, vp, vp, vp, vp, vp]
+    L.sml_quantize_pack_frames_typed.restype = i32
+    L.sml_quantize_pack_frames_typed.argtypes = [vp, i32, u64, u32, u16, vp, u32, ctypes.POINTER(FrameParams), vp, u64,
+                                                 vp]
+    L.sml_dequantize_frames_typed.restype = i32
+    L.sml_dequantize_frames_typed.argtypes = [vp, u64, u64, u64, u32, u16, u32, u64, vp, vp, vp, i32, vp, vp]
     L.sml_rx_reset.restype = i32
     L.sml_rx_reset.argtypes = [vp, u64, vp]
     L.sml_pack_frames_int32.restype = i32
@@ -680,7 +685,8 @@ def quantize_pack_frames(x, params: FrameParams, packet_numel: int = 256, num_wo
                          stream=None):
     """Fused quantize + pack straight into DPDK frames (B + b frames of
     `stride` bytes, uint8).  `frames` may be a device tensor or pinned host
-    memory (the NIC's buffers)."""
+    memory (the NIC's buffers).  `x` is fp32, or fp16 / bf16 (widened inside
+    the kernel: the frames are those of x.float())."""
     torch = _torch()
     B = num_blocks(x.numel(), packet_numel)
     b = min(B, batch_max)
@@ -688,6 +694,12 @@ def quantize_pack_frames(x, params: FrameParams, packet_numel: int = 256, num_wo
     if frames is None:
         frames = torch.empty((B + b) * stride, dtype=torch.uint8, device=x.device)
     g = None if global_exps is None else _dev(global_exps, torch.int8, "global_exps")
+    dt = _float_type(x.dtype, "x")
+    if dt != FLOAT32:
+        _check("sml_quantize_pack_frames_typed", lib().sml_quantize_pack_frames_typed(
+            _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, num_workers, g, batch_max,
+            ctypes.byref(params), _dev(frames, torch.uint8, "frames"), stride, _stream(stream, x)))
+        return frames
     _check("sml_quantize_pack_frames", lib().sml_quantize_pack_frames(
         _dev(x, torch.float32, "x"), x.numel(), packet_numel, num_workers, g, batch_max,
         ctypes.byref(params), _dev(frames, torch.uint8, "frames"), stride, _stream(stream, x)))
@@ -697,18 +709,25 @@ def quantize_pack_frames(x, params: FrameParams, packet_numel: int = 256, num_wo
 class RxSlice:
     """Receive-side state of one job slice for dequantize_frames: the
     received exponents, the rx bitmap (DpdkWorkerThread's rte_bitmap,
-    dpdk_worker_thread.cc:316-342) and {accepted, discarded} counters."""
+    dpdk_worker_thread.cc:316-342) and {accepted, discarded} counters.
+    `dtype` is the output's element type: fp32, or fp16 / bf16 (narrowed
+    inside the kernel); a given `out` must be of it."""
 
     def __init__(self, numel: int, packet_numel: int = 256, batch_max: int = 64, device="cuda",
-                 out=None):
+                 out=None, dtype=None):
         torch = _torch()
+        dtype = dtype or (out.dtype if out is not None else torch.float32)
+        _float_type(dtype, "dtype")
+        if out is not None and out.dtype != dtype:
+            raise TypeError(f"out is {out.dtype}, dtype {dtype}")
+        self.dtype = dtype
         self.numel, self.packet_numel, self.batch_max = numel, packet_numel, batch_max
         B = num_blocks(numel, packet_numel)
         self.exps = torch.zeros(B, dtype=torch.int8, device=device)
         self.state = torch.zeros(int(lib().sml_rx_state_words(numel, packet_numel, batch_max, 0)),
                                  dtype=torch.int64, device=device)
         self.counts = torch.zeros(2, dtype=torch.int64, device=device)
-        self.out = out if out is not None else torch.zeros(numel, dtype=torch.float32, device=device)
+        self.out = out if out is not None else torch.zeros(numel, dtype=dtype, device=device)
 
     def reset(self, stream=None):
         """rte_bitmap_reset for a new job slice: zero the rx state (one async
@@ -721,9 +740,17 @@ class RxSlice:
 def dequantize_frames(frames, num_frames: int, rx: RxSlice, num_workers: int = 1, job_id: int = 0,
                       stride: int | None = None, stream=None):
     """PostprocessSingle over received DPDK frames (any order; duplicates and
-    other jobs' frames discarded), writing rx.out / rx.exps / rx.counts."""
+    other jobs' frames discarded), writing rx.out / rx.exps / rx.counts.
+    An fp16 / bf16 rx.out is narrowed inside the kernel."""
     torch = _torch()
     stride = stride or frame_bytes(rx.packet_numel)
+    dt = _float_type(rx.out.dtype, "rx.out")
+    if dt != FLOAT32:
+        _check("sml_dequantize_frames_typed", lib().sml_dequantize_frames_typed(
+            _dev(frames, torch.uint8, "frames"), num_frames, stride, rx.numel, rx.packet_numel, num_workers,
+            rx.batch_max, job_id, _dev(rx.exps, torch.int8, "exps"), _dev(rx.state, torch.int64, "state"),
+            _dev(rx.out, rx.out.dtype, "out"), dt, _dev(rx.counts, torch.int64, "counts"), _stream(stream, rx.out)))
+        return rx.out
     _check("sml_dequantize_frames", lib().sml_dequantize_frames(
         _dev(frames, torch.uint8, "frames"), num_frames, stride, rx.numel, rx.packet_numel, num_workers,
         rx.batch_max, job_id, _dev(rx.exps, torch.int8, "exps"), _dev(rx.state, torch.int64, "state"),
