@@ -203,7 +203,8 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
  * round trip.  Batches of 16-bit slices go through
  * sml_roundtrip_loopback_batch_typed (below), DPDK frames through
  * sml_quantize_pack_frames_typed / sml_dequantize_frames_typed (with the
- * frames, below).  A 16-bit slice's RDMA messages need no entry point of
+ * frames, below), the in-node switch's multicast of a 16-bit shard through
+ * sml_copy_segments_typed (with sml_copy_segments, below).  A 16-bit slice's RDMA messages need no entry point of
  * their own: sml_quantize_pack_typed at packet_numel = msg_numel gives the
  * message payloads and sml_rdma_imm on its exponent plane the immediates.
  * The burst entry points and sml_roundtrip_loopback_batch take no 16-bit type
@@ -282,6 +283,22 @@ sml_status_t sml_copy_words(const void* d_src, void* d_dst, uint64_t num_words, 
  * shards come over their xGMI links at the same time, not one after another. */
 sml_status_t sml_copy_segments(const void* const* d_srcs, void* const* d_dsts, const uint64_t* num_words,
                                uint32_t num_segments, uint32_t flags, void* stream);
+
+/* The same multicast for a job of any type: d_dsts[i][0..n_i) =
+ * d_srcs[i][0..n_i) as elements of data_type, n_i = numel[i].
+ *   SML_FLOAT32 / SML_INT32: forwards to sml_copy_segments (same kernel,
+ *     checks and bits).
+ *   SML_FLOAT16 / SML_BFLOAT16: 2-byte elements.  A 16-bit shard ends on an
+ *     odd element and lands in a slice that starts at any element, so every
+ *     source and destination needs 2-byte alignment only, each independently,
+ *     and n_i may be odd; no byte outside [dst, dst + 2 n_i) is written, none
+ *     outside [src, src + 2 n_i) read.  Empty segments touch nothing; segments
+ *     must not overlap.
+ * Any other type: SML_ERR_UNSUPPORTED.  A NULL table, a NULL or odd pointer
+ * with n_i > 0, or more than SML_MAX_SWITCH_WORKERS segments:
+ * SML_ERR_INVALID_ARG.  Every check precedes the launch. */
+sml_status_t sml_copy_segments_typed(const void* const* d_srcs, void* const* d_dsts, const uint64_t* numel,
+                                     uint32_t num_segments, sml_data_type_t data_type, uint32_t flags, void* stream);
 
 /* The writer's half of a hand-off to other GPUs: a system-scope release on
  * every XCD of the stream's device (each XCD's L2 writes its dirty lines back

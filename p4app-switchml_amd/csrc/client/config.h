@@ -92,6 +92,13 @@ struct XgmiBackendConfig {
     // xGMI and K6 reads only local HBM (push).  Same bytes; all workers of a
     // session must agree.  The multicast (gather) pulls in both.
     bool push = false;
+    // FLOAT16 / BFLOAT16 jobs across the workers: false = such a job is
+    // refused (it ends FAILED, the tensor untouched); true = it runs the
+    // FLOAT32 exchange with the kernels converting (K2 / K3 widen, K6 narrows
+    // once, at the shard's owner, into a 16-bit out plane; the multicast
+    // moves 2-byte elements, sml_copy_segments_typed).  All workers of a
+    // session must agree.
+    bool half_types = false;
     // Fault injection for tests: this worker fails right after joining the
     // session (handles published, the workers' barrier passed), as one that
     // cannot map a peer's plane on its first contact with another GPU does.
@@ -118,9 +125,12 @@ class Config {
     void Validate();
     // Whether this configuration runs FLOAT16 / BFLOAT16 jobs: the dummy
     // backend's bulk and fused modes convert them inside the kernels (and the
-    // bypass PPP moves no data, whatever the mode); mode = packet and
-    // backend = xgmi refuse such a job, which then ends FAILED.
+    // bypass PPP moves no data, whatever the mode), and the in-node switch
+    // exchanges them when backend.xgmi.half_types is set (it needs the HIP
+    // PPP: Validate); mode = packet and backend = xgmi without half_types
+    // refuse such a job, which then ends FAILED.
     bool RunsHalfTypes() const {
+        if (general_.backend == "xgmi") return backend_.xgmi.half_types && general_.prepostprocessor != "bypass";
         return general_.backend == "dummy" && (general_.prepostprocessor == "bypass" ||
                                                backend_.hip.mode == "bulk" || backend_.hip.mode == "fused");
     }

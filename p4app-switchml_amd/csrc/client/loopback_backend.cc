@@ -170,9 +170,11 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
     Tensor& t = js.slice;
     const std::string& mode = cfg.backend_.hip.mode;
     // FLOAT16 / BFLOAT16: the bulk hooks and the fused round trip convert
-    // inside the kernels; the per-packet loop's first burst hook and the
-    // in-node switch (XgmiSwitch::AllReduceSlice) throw for such a slice,
-    // before anything is written, rather than run it as another type
+    // inside the kernels, and so does the in-node switch under
+    // backend.xgmi.half_types; the per-packet loop's first burst hook and the
+    // in-node switch without that key (XgmiSwitch::AllReduceSlice) throw for
+    // such a slice, before anything is written, rather than run it as
+    // another type
     const size_t bytes = t.numel * DataTypeSize(t.data_type);
     // Device tensors are used in place; pinned host tensors too, through
     // their device mapping (the kernels read and write them over PCIe, both

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <thread>
 
+#include "hip_exponent_quantizer_ppp.h"
 #include "hip_util.h"
 
 namespace switchml {
@@ -60,6 +61,8 @@ struct XgmiShm {
     std::atomic<uint32_t> attached;
     std::atomic<uint32_t> detached;
     uint32_t push;                         // backend.xgmi.push of worker 0 (every worker must match)
+    uint32_t half_types;                   // backend.xgmi.half_types of worker 0 (likewise)
+    std::atomic<uint32_t> disagree;        // a worker's configuration does not match worker 0's: every worker fails setup
     ShmBarrier bar[kMaxT + 1];             // [t]: worker thread t; [kMaxT]: setup / teardown
     ShmPlanes planes[kMaxW][kMaxT];
 };
@@ -111,6 +114,7 @@ void XgmiSwitch::OpenSegment() {
                 shm_->P = P_;
                 shm_->cap = cap_;
                 shm_->push = push_ ? 1u : 0u;
+                shm_->half_types = half_types_ ? 1u : 0u;
                 shm_->creator_pid.store(getpid());
                 shm_->magic.store(kMagic, std::memory_order_release);
                 return;
@@ -164,6 +168,7 @@ XgmiSwitch::XgmiSwitch(const Config& config, int device) {
     timeout_ms_ = config.backend_.xgmi.timeout_ms;
     round_flags_ = config.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u;
     push_ = config.backend_.xgmi.push;
+    half_types_ = config.backend_.xgmi.half_types;
     fail_setup_ = config.backend_.xgmi.fail_setup;
     if (W_ < 1 || W_ > kMaxW) Fatal("num_workers must be 1..16");
     if (T_ < 1 || T_ > kMaxT) Fatal("num_worker_threads must be 1..16");
@@ -220,11 +225,17 @@ void XgmiSwitch::Setup(int device) {
     // failed must not free its exported planes while a peer is still inside
     // hipIpcOpenMemHandle on them — the importer then hangs in the runtime
     // (measured on MI355X, the N = 8 first-contact rehearsal: > 90 s).
+    // A worker that differs from worker 0 says so in the segment, so that
+    // every worker (worker 0 included, which cannot see it otherwise) fails
+    // setup with the same error once all have compared.
+    const char* disagree =
+        "workers disagree on num_workers / num_worker_threads / packet_numel / max_slice_numel / push / half_types";
     std::string err;
     if (shm_->W != (uint32_t)W_ || shm_->T != (uint32_t)T_ || shm_->P != P_ || shm_->cap != cap_ ||
-        shm_->push != (push_ ? 1u : 0u))
-        err = "workers disagree on num_workers / num_worker_threads / packet_numel / max_slice_numel / push";
-    else if (fail_setup_)
+        shm_->push != (push_ ? 1u : 0u) || shm_->half_types != (half_types_ ? 1u : 0u)) {
+        shm_->disagree.store(1, std::memory_order_release);
+        err = disagree;
+    } else if (fail_setup_)
         err = "injected setup failure (backend.xgmi.fail_setup)";
     else
         try {
@@ -232,7 +243,12 @@ void XgmiSwitch::Setup(int device) {
         } catch (const std::exception& e) {
             err = e.what();
         }
-    Barrier(kMaxT);   // every worker is done importing
+    try {
+        Barrier(kMaxT);   // every worker is done importing
+    } catch (const std::exception& e) {
+        if (err.empty()) err = e.what();
+    }
+    if (shm_->disagree.load(std::memory_order_acquire)) err = disagree;
     if (!err.empty()) throw SwitchMLFatal(err.rfind(kWho, 0) == 0 ? err : kWho + err);
 }
 
@@ -417,6 +433,13 @@ namespace {
 // this GPU's L2 back before the stream sync that precedes the barrier.
 void release(hipStream_t st) { sml_ok(sml_release_to_peers(st), "sml_release_to_peers", kWho); }
 constexpr uint32_t kPeer = SML_FLAG_PEER_PLANES;   // the reader's half: acquire in the reading kernels
+
+// Element `i` of a buffer of `type` elements (a tensor slice, or an out plane:
+// cap_ floats, which a 16-bit slice uses as a plane of cap_ 2-byte elements).
+const void* at(const void* p, uint64_t i, DataType type) { return static_cast<const char*>(p) + i * DataTypeSize(type); }
+void* at(void* p, uint64_t i, DataType type) { return static_cast<char*>(p) + i * DataTypeSize(type); }
+// What the typed copy takes: a float type as the kernels know it, INT32 as itself.
+sml_data_type_t CopyType(DataType type) { return type == INT32 ? SML_INT32 : SmlFloatType(type); }
 }  // namespace
 
 // The end of every phase of an exchange: release what the phase wrote for
@@ -432,12 +455,14 @@ void XgmiSwitch::HandOff(int tid, std::initializer_list<PhaseStream> streams) {
 // The switch's exponent max over the W planes into gexp, then K3: quantize
 // with the global exponents into the own BE payload plane (pull), or each
 // shard w straight into row `rank` of worker w's inbox (push: one K3 launch
-// per shard, W − 1 of them writing over xGMI).
-void XgmiSwitch::Quantize(ThreadPlanes& tp, const float* in, const ShardPlan& plan, hipStream_t st) {
+// per shard, W − 1 of them writing over xGMI).  `in` holds elements of
+// `type` (a float type; FLOAT32 forwards to sml_quantize_pack).
+void XgmiSwitch::Quantize(ThreadPlanes& tp, const void* in, DataType type, const ShardPlan& plan, hipStream_t st) {
     const uint16_t W = (uint16_t)W_;
+    const sml_data_type_t dt = SmlFloatType(type);
     sml_ok(sml_switch_exps(tp.peer_exps.data(), W, plan.B, tp.gexp, kPeer, st), "sml_switch_exps", kWho);
     if (!push_) {
-        sml_ok(sml_quantize_pack(in, plan.n, P_, W, tp.gexp, tp.payload, nullptr, round_flags_, st),
+        sml_ok(sml_quantize_pack_typed(in, dt, plan.n, P_, W, tp.gexp, tp.payload, nullptr, round_flags_, st),
                "sml_quantize_pack", kWho);
         return;
     }
@@ -445,14 +470,15 @@ void XgmiSwitch::Quantize(ThreadPlanes& tp, const float* in, const ShardPlan& pl
         const Shard sh = plan.shard(w);
         if (!sh.nb) continue;
         int32_t* row = const_cast<int32_t*>(tp.peer_payload[w]) + plan.inbox_row(rank_);
-        sml_ok(sml_quantize_pack(in + sh.offset, sh.numel, P_, W, tp.gexp + sh.b0, row, nullptr, round_flags_, st),
-               "sml_quantize_pack", kWho);
+        sml_ok(sml_quantize_pack_typed(at(in, sh.offset, type), dt, sh.numel, P_, W, tp.gexp + sh.b0, row, nullptr,
+                                       round_flags_, st), "sml_quantize_pack", kWho);
     }
 }
 
 // K6: the wrapping sum of this worker's shard over the W planes, dequantized
-// into the own output plane.
-void XgmiSwitch::Aggregate(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st) {
+// into the own output plane as elements of `type` (a 16-bit type: narrowed
+// here, once, so every worker ends with the owner's bits).
+void XgmiSwitch::Aggregate(ThreadPlanes& tp, DataType type, const ShardPlan& plan, hipStream_t st) {
     const Shard sh = plan.shard(rank_);
     if (!sh.nb) return;
     const int32_t* planes[kMaxW];
@@ -462,11 +488,14 @@ void XgmiSwitch::Aggregate(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t 
         planes[w] = push_ ? tp.payload + plan.inbox_row(w) : tp.peer_payload[w] + sh.offset;
         exps[w] = tp.gexp + sh.b0;
     }
-    sml_ok(sml_switch_aggregate(planes, exps, (uint16_t)W_, sh.numel, P_, nullptr, nullptr, tp.out + sh.offset,
-                                kPeer, st), "sml_switch_aggregate", kWho);
+    sml_ok(sml_switch_aggregate_typed(planes, exps, (uint16_t)W_, sh.numel, P_, nullptr, nullptr,
+                                      at(tp.out, sh.offset, type), SmlFloatType(type), kPeer, st),
+           "sml_switch_aggregate", kWho);
 }
 
-// A FLOAT32 slice, chunk by chunk, pipelined on two streams (the caller's
+// A slice of a float type (FLOAT32, or FLOAT16 / BFLOAT16 under
+// backend.xgmi.half_types: the kernels convert, the out plane and the
+// multicast carry 2-byte elements), chunk by chunk, pipelined on two streams (the caller's
 // `st` for the local HBM work, tp.xst for the xGMI phases):
 //   prologue   K2(0) | barrier | max + K3(0) | barrier
 //   chunk c    K6(c) on xst  beside  K2(c+1) on st          | barrier
@@ -483,27 +512,28 @@ void XgmiSwitch::Aggregate(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t 
 // Each "| barrier" is one HandOff.  What xst wrote for the peers (K6's shard)
 // is released as soon as it is queued, before the next chunk's work is
 // enqueued on st; the gather writes the caller's tensor, which no peer reads.
-void XgmiSwitch::FloatSlice(int tid, const float* in, float* out, uint64_t numel, hipStream_t st) {
+void XgmiSwitch::FloatSlice(int tid, const void* in, void* out, uint64_t numel, DataType type, hipStream_t st) {
     ThreadPlanes& tp = planes_[tid];
     const hipStream_t xst = tp.xst;
     const uint64_t nchunks = (numel + cap_ - 1) / cap_;
     auto plan = [&](uint64_t c) { return ShardPlan(std::min<uint64_t>(cap_, numel - c * cap_), P_, (uint64_t)W_); };
     auto k2 = [&](uint64_t c) {
-        sml_ok(sml_exponents(in + c * cap_, plan(c).n, P_, tp.exps, st), "sml_exponents", kWho);
+        sml_ok(sml_exponents_typed(at(in, c * cap_, type), SmlFloatType(type), plan(c).n, P_, tp.exps, st),
+               "sml_exponents", kWho);
     };
-    auto k3 = [&](uint64_t c) { Quantize(tp, in + c * cap_, plan(c), st); };   // the max, then K3
+    auto k3 = [&](uint64_t c) { Quantize(tp, at(in, c * cap_, type), type, plan(c), st); };   // the max, then K3
     auto k6 = [&](uint64_t c) {
-        Aggregate(tp, plan(c), xst);
-        if (push_) PushShard(tp, plan(c), xst);   // the multicast, as writes into the peers' out planes
+        Aggregate(tp, type, plan(c), xst);
+        if (push_) PushShard(tp, type, plan(c), xst);   // the multicast, as writes into the peers' out planes
         release(xst);
     };
     auto gather = [&](uint64_t c) {
-        if (!push_) return Gather(tp, out + c * cap_, plan(c), xst);
+        if (!push_) return Gather(tp, at(out, c * cap_, type), type, plan(c), xst);
         // every shard is in the own out plane now: one local copy
         const void* src = tp.out;
-        void* dst = out + c * cap_;
+        void* dst = at(out, c * cap_, type);
         const uint64_t n = plan(c).n;
-        sml_ok(sml_copy_segments(&src, &dst, &n, 1, kPeer, xst), "sml_copy_segments", kWho);
+        sml_ok(sml_copy_segments_typed(&src, &dst, &n, 1, CopyType(type), kPeer, xst), "sml_copy_segments", kWho);
     };
     k2(0);
     HandOff(tid, {{st, true}});
@@ -524,7 +554,7 @@ void XgmiSwitch::FloatSlice(int tid, const float* in, float* out, uint64_t numel
 // out plane) written into the same place of every peer's out plane (W − 1
 // segments in one launch, over xGMI), so that after the next barrier every
 // out plane holds all W shards.
-void XgmiSwitch::PushShard(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st) {
+void XgmiSwitch::PushShard(ThreadPlanes& tp, DataType type, const ShardPlan& plan, hipStream_t st) {
     const Shard sh = plan.shard(rank_);
     if (!sh.nb || W_ == 1) return;
     const void* srcs[kMaxW];
@@ -533,30 +563,31 @@ void XgmiSwitch::PushShard(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t 
     uint32_t k = 0;
     for (int w = 0; w < W_; w++) {
         if (w == rank_) continue;
-        srcs[k] = tp.out + sh.offset;
-        dsts[k] = const_cast<float*>(tp.peer_out[w]) + sh.offset;
+        srcs[k] = at(tp.out, sh.offset, type);
+        dsts[k] = at(const_cast<float*>(tp.peer_out[w]), sh.offset, type);
         cnt[k] = sh.numel;
         k++;
     }
-    sml_ok(sml_copy_segments(srcs, dsts, cnt, k, 0, st), "sml_copy_segments", kWho);
+    sml_ok(sml_copy_segments_typed(srcs, dsts, cnt, k, CopyType(type), 0, st), "sml_copy_segments", kWho);
 }
 
 // Worker w's shard of every plane (blocks [w S, min((w+1) S, B))) from its
-// out plane into `out`, one sml_copy_segments launch for the W shards.
-void XgmiSwitch::Gather(ThreadPlanes& tp, void* out, const ShardPlan& plan, hipStream_t st) {
+// out plane into `out`, one sml_copy_segments_typed launch for the W shards
+// (elements of `type`: 32-bit words, or a 16-bit slice's 2-byte elements).
+void XgmiSwitch::Gather(ThreadPlanes& tp, void* out, DataType type, const ShardPlan& plan, hipStream_t st) {
     const void* srcs[kMaxW];
     void* dsts[kMaxW];
-    uint64_t words[kMaxW];
+    uint64_t cnt[kMaxW];
     uint32_t k = 0;
     for (int w = 0; w < W_; w++) {
         const Shard sh = plan.shard(w);
         if (!sh.nb) continue;
-        srcs[k] = reinterpret_cast<const uint32_t*>(tp.peer_out[w]) + sh.offset;
-        dsts[k] = static_cast<uint32_t*>(out) + sh.offset;
-        words[k] = sh.numel;
+        srcs[k] = at(tp.peer_out[w], sh.offset, type);
+        dsts[k] = at(out, sh.offset, type);
+        cnt[k] = sh.numel;
         k++;
     }
-    sml_ok(sml_copy_segments(srcs, dsts, words, k, kPeer, st), "sml_copy_segments", kWho);
+    sml_ok(sml_copy_segments_typed(srcs, dsts, cnt, k, CopyType(type), kPeer, st), "sml_copy_segments", kWho);
 }
 
 // An INT32 chunk, on the caller's stream alone:
@@ -580,23 +611,24 @@ void XgmiSwitch::IntChunk(int tid, const int32_t* in, int32_t* out, uint64_t n, 
                                     SML_FLAG_PAYLOAD_LE | kPeer, st), "sml_switch_aggregate", kWho);
     }
     HandOff(tid, {{st, sh.nb != 0}});
-    Gather(tp, out, plan, st);
+    Gather(tp, out, INT32, plan, st);
     HandOff(tid, {{st, false}});
 }
 
 void XgmiSwitch::AllReduceSlice(int tid, const void* in, void* out, uint64_t numel, DataType type, hipStream_t st) {
     if (tid < 0 || tid >= T_) Fatal("bad worker thread id");
-    // every worker refuses the same job here, before any barrier (the CollNet
-    // plugin never posts one: its reduceSupport is 0 for these types under xgmi)
-    if (IsHalfType(type))
+    // without backend.xgmi.half_types every worker refuses the same job here,
+    // before any barrier (the CollNet plugin never posts one: its
+    // reduceSupport is then 0 for these types under xgmi)
+    if (IsHalfType(type) && !half_types_)
         Fatal(std::string(DataTypeName(type)) +
               " jobs are not supported with backend = xgmi; use backend = dummy (mode bulk or fused)");
     if (numel == 0) return;
     if (Wedged()) Fatal("an earlier slice's device work did not finish");
     ThrowIfPoisoned();
     try {
-        if (type == FLOAT32) {
-            FloatSlice(tid, static_cast<const float*>(in), static_cast<float*>(out), numel, st);
+        if (IsFloatType(type)) {
+            FloatSlice(tid, in, out, numel, type, st);
             return;
         }
         for (uint64_t off = 0; off < numel; off += cap_) {

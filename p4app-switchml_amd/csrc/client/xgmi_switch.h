@@ -37,7 +37,21 @@
 //     peer's out plane, and the gather becomes one local copy; same phases,
 //     barriers and bytes, every xGMI transfer a write;
 //   * INT32 slices: the words themselves are summed (the INT32 PPP only
-//     reorders bytes, ppp.cc:158-190, 262-298), pulled in both forms.
+//     reorders bytes, ppp.cc:158-190, 262-298), pulled in both forms;
+//   * FLOAT16 / BFLOAT16 slices (opt-in, backend.xgmi.half_types, every
+//     worker alike; refused without it): the FLOAT32 pipeline with the element
+//     type as a parameter — same chunks, streams, hand-offs and barriers.  K2
+//     and K3 widen after the load (sml_exponents_typed,
+//     sml_quantize_pack_typed), so the planes on the wire are the FLOAT32
+//     ones; K6 narrows (round to nearest even) into the out plane, whose cap
+//     floats serve as cap 2-byte elements, shard w at the same element offset
+//     in every worker's plane; the multicast — gather, shard push and the push
+//     form's local copy — moves 2-byte elements (sml_copy_segments_typed: a
+//     shard ends on an odd element and lands at any 2-byte offset of the
+//     tensor), half the fp32 bytes over xGMI.  A value is rounded once, at its
+//     owner, so every worker ends with identical bits.  Planes, handles and
+//     the session segment's layout do not grow; slices of any type follow
+//     each other on one session.
 // Results are bit-identical to the oracle's W-worker software switch
 // (orc_switch_exps / orc_switch_payload + dequantize), slice by slice.
 //
@@ -115,7 +129,7 @@ class XgmiSwitch {
         // rows of S blocks, row r = worker r's quantized share of this
         // worker's shard
         int32_t* payload = nullptr;
-        float* out = nullptr;
+        float* out = nullptr;          // cap_ floats; a 16-bit slice uses it as cap_ 2-byte elements
         int8_t* gexp = nullptr;        // local: the global exponents
         std::vector<const int8_t*> peer_exps;      // [W], own included
         std::vector<const int32_t*> peer_payload;  // [W]
@@ -147,12 +161,14 @@ class XgmiSwitch {
     bool StreamSync(hipStream_t st, bool bounded_only = false);
     void HandOff(int tid, std::initializer_list<PhaseStream> streams);
     // The chunk's shards (which blocks each worker owns) come from xgmi_shards.h.
-    void FloatSlice(int tid, const float* in, float* out, uint64_t numel, hipStream_t st);
-    void Aggregate(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st);
-    void Quantize(ThreadPlanes& tp, const float* in, const ShardPlan& plan, hipStream_t st);
+    // `type`: the slice's element type (FloatSlice: a float type), which the
+    // typed kernels convert from and to.
+    void FloatSlice(int tid, const void* in, void* out, uint64_t numel, DataType type, hipStream_t st);
+    void Aggregate(ThreadPlanes& tp, DataType type, const ShardPlan& plan, hipStream_t st);
+    void Quantize(ThreadPlanes& tp, const void* in, DataType type, const ShardPlan& plan, hipStream_t st);
     void IntChunk(int tid, const int32_t* in, int32_t* out, uint64_t n, hipStream_t st);
-    void Gather(ThreadPlanes& tp, void* out, const ShardPlan& plan, hipStream_t st);
-    void PushShard(ThreadPlanes& tp, const ShardPlan& plan, hipStream_t st);
+    void Gather(ThreadPlanes& tp, void* out, DataType type, const ShardPlan& plan, hipStream_t st);
+    void PushShard(ThreadPlanes& tp, DataType type, const ShardPlan& plan, hipStream_t st);
 
     int rank_, W_, T_;
     int device_ = -1;
@@ -161,6 +177,7 @@ class XgmiSwitch {
     uint64_t timeout_ms_;
     uint32_t round_flags_ = 0;   // SML_FLAG_ROUND_RNE under backend.hip.vcl
     bool push_ = false;     // backend.xgmi.push: K3 writes into the owners' inboxes
+    bool half_types_ = false;   // backend.xgmi.half_types: FLOAT16 / BFLOAT16 slices are exchanged, not refused
     bool fail_setup_ = false;   // backend.xgmi.fail_setup (fault injection)
     std::string name_;
     XgmiShm* shm_ = nullptr;

@@ -251,6 +251,65 @@ __global__ __launch_bounds__(kBlockThreads) void k_copy_segments(SegCopyArgs a) 
     }
 }
 
+// The multicast of a FLOAT16 / BFLOAT16 slice (sml_copy_segments_typed): the
+// same deal of tiles over the segments, on 2-byte elements.  A 16-bit shard
+// ends on an odd element and lands in a tensor slice that starts at any
+// element, so both sides are 2-byte aligned only, independently: full tiles
+// move one vector of kSegVec16 elements per lane per slice through a type
+// declared 2-byte aligned (gfx950's unaligned-access mode keeps it one
+// global_load_dwordx2 and one global_store_dwordx2), the last partial tile
+// goes element by element.  The bits are copied, so one instance serves both
+// types.  8 bytes per lane, the 16-bit plane kernels' access (h4a): a build
+// with 16 (kSegVec16 = 8: dwordx4, 80 VGPRs) was not faster beyond the
+// rounds' ranges on 8 segments of 2 Mi elements at an odd destination
+// (profiles/half/bench_half_xgmi.json).
+constexpr int kSegVec16 = 4;   // elements per lane per slice
+constexpr int kSegTile16 = kWave * kSegVec16 * kU;   // 1024
+typedef uint16_t hva __attribute__((ext_vector_type(kSegVec16), aligned(2)));
+
+struct SegCopy16Args {
+    const uint16_t* src[SML_MAX_SWITCH_WORKERS];
+    uint16_t* dst[SML_MAX_SWITCH_WORKERS];
+    uint64_t n[SML_MAX_SWITCH_WORKERS];
+    uint32_t nseg;
+    uint64_t ntiles;        // nseg x (the largest segment's groups) x kSegGroup
+    uint32_t xcd;
+    uint32_t flags;
+};
+
+__global__ __launch_bounds__(kBlockThreads) void k_copy_segments16(SegCopy16Args a) {
+    acquire_peer_planes(a.flags);
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
+    for (uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index(); t < a.ntiles; t += nwaves) {
+        const uint64_t g = t / kSegGroup;
+        const uint32_t s = (uint32_t)(g % a.nseg);
+        const uint64_t base = ((g / a.nseg) * kSegGroup + t % kSegGroup) * (uint64_t)kSegTile16;
+        const uint64_t n = a.n[s];
+        if (base >= n) continue;
+        const uint16_t* in = a.src[s];
+        uint16_t* out = a.dst[s];
+        if (base + kSegTile16 <= n) {
+            hva v[kU];
+#pragma unroll
+            for (int u = 0; u < kU; u++)
+                v[u] = __builtin_nontemporal_load(
+                    reinterpret_cast<const hva*>(in + base + (u * kWave + lane) * kSegVec16));
+#pragma unroll
+            for (int u = 0; u < kU; u++)
+                *reinterpret_cast<hva*>(out + base + (u * kWave + lane) * kSegVec16) = v[u];
+        } else {
+#pragma unroll
+            for (int u = 0; u < kU; u++)
+#pragma unroll
+                for (int j = 0; j < kSegVec16; j++) {
+                    const uint64_t idx = base + (uint64_t)(u * kWave + lane) * kSegVec16 + j;
+                    if (idx < n) out[idx] = in[idx];
+                }
+        }
+    }
+}
+
 // ncclUint8 buckets (the CollNet plugin, switchml_plugin.cc:318-337 and
 // 370-378): widened to int32 for the INT32 all-reduce, narrowed back (mod 256).
 __global__ __launch_bounds__(kBlockThreads) void k_widen_u8(const uint8_t* in, int32_t* out, uint64_t n) {
@@ -418,6 +477,36 @@ sml_status_t sml_copy_segments(const void* const* d_srcs, void* const* d_dsts, c
     a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
     a.flags = flags & SML_FLAG_PEER_PLANES;
     k_copy_segments<<<grid_for_tiles(a.ntiles), kBlockThreads, 0, (hipStream_t)stream>>>(a);
+    return launch_check();
+}
+
+sml_status_t sml_copy_segments_typed(const void* const* d_srcs, void* const* d_dsts, const uint64_t* numel,
+                                     uint32_t num_segments, sml_data_type_t data_type, uint32_t flags, void* stream) {
+    if (data_type == SML_FLOAT32 || data_type == SML_INT32)
+        return sml_copy_segments(d_srcs, d_dsts, numel, num_segments, flags, stream);
+    if (!is_half(data_type)) return SML_ERR_UNSUPPORTED;
+    if (num_segments == 0) return SML_OK;
+    if (!d_srcs || !d_dsts || !numel || num_segments > SML_MAX_SWITCH_WORKERS) return SML_ERR_INVALID_ARG;
+    SegCopy16Args a;
+    a.nseg = 0;
+    uint64_t groups = 0;
+    const uint64_t ge = (uint64_t)kSegGroup * kSegTile16;   // elements per group
+    for (uint32_t i = 0; i < num_segments; i++) {
+        if (numel[i] == 0) continue;                        // empty segments touch nothing
+        if (!d_srcs[i] || !d_dsts[i] || ((uintptr_t)d_srcs[i] & 1u) || ((uintptr_t)d_dsts[i] & 1u))
+            return SML_ERR_INVALID_ARG;
+        a.src[a.nseg] = static_cast<const uint16_t*>(d_srcs[i]);
+        a.dst[a.nseg] = static_cast<uint16_t*>(d_dsts[i]);
+        a.n[a.nseg] = numel[i];
+        const uint64_t gi = (numel[i] + ge - 1) / ge;
+        groups = gi > groups ? gi : groups;
+        a.nseg++;
+    }
+    if (a.nseg == 0) return SML_OK;
+    a.ntiles = (uint64_t)a.nseg * groups * kSegGroup;
+    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
+    a.flags = flags & SML_FLAG_PEER_PLANES;
+    k_copy_segments16<<<grid_for_tiles(a.ntiles), kBlockThreads, 0, (hipStream_t)stream>>>(a);
     return launch_check();
 }
 

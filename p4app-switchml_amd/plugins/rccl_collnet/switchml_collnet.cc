@@ -256,7 +256,7 @@ bool runs_half_types() {
 ncclResult_t sml_reduce_support(ncclDataType_t dtype, ncclRedOp_t op, int* supported) {
     // fp16 / bf16 need no widening buffer: the client's kernels convert — in
     // the configurations that run them (Config::RunsHalfTypes).  Elsewhere
-    // (backend = xgmi, mode = packet) the answer stays 0, as before these
+    // (backend = xgmi without backend.xgmi.half_types, mode = packet) the answer stays 0, as before these
     // types existed, so RCCL reduces such buckets with its own algorithms
     // instead of posting jobs here that would end FAILED.
     const bool half = dtype == ncclFloat16 || dtype == ncclBfloat16;

@@ -173,6 +173,8 @@ def lib():
     L.sml_switch_aggregate_typed.argtypes = [vp, vp, u16, u64, u32, vp, vp, vp, i32, u32, vp]
     L.sml_copy_segments.restype = i32
     L.sml_copy_segments.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.sml_copy_segments_typed.restype = i32
+    L.sml_copy_segments_typed.argtypes = [vp, vp, vp, u32, i32, u32, vp]
     L.sml_switch_exps.restype = i32
     L.sml_switch_exps.argtypes = [vp, u16, u64, vp, u32, vp]
     L.sml_release_to_peers.restype = i32
@@ -576,6 +578,35 @@ def copy_segments(pairs, flags: int = 0, stream=None):
     _check("sml_copy_segments", lib().sml_copy_segments(
         ctypes.cast(srcs, ctypes.c_void_p), ctypes.cast(dsts, ctypes.c_void_p), ctypes.cast(words, ctypes.c_void_p),
         k, flags, _stream(stream, pairs[0][0] if pairs else None)))
+
+
+def copy_segments_typed(pairs, flags: int = 0, stream=None):
+    """sml_copy_segments_typed: every (src, dst) pair of tensors of one dtype
+    (same numel; CUDA or pinned host) copied in ONE launch.  float16 /
+    bfloat16 pairs may start at any element (views at odd offsets) and hold
+    an odd number of elements; float32 / int32 pairs go to sml_copy_segments'
+    kernel.  The in-node switch's multicast of a job of that type."""
+    torch = _torch()
+    k = len(pairs)
+    if k > MAX_SWITCH_WORKERS:
+        raise ValueError(f"at most {MAX_SWITCH_WORKERS} segments")
+    dtypes = {t.dtype for pair in pairs for t in pair}
+    if len(dtypes) > 1:
+        raise TypeError(f"segments are tensors of one dtype, got {sorted(map(str, dtypes))}")
+    dtype = dtypes.pop() if dtypes else torch.float32
+    dt = INT32 if dtype == torch.int32 else _float_type(dtype, "segments")
+    srcs = (ctypes.c_void_p * max(1, k))()
+    dsts = (ctypes.c_void_p * max(1, k))()
+    numel = (ctypes.c_uint64 * max(1, k))()
+    for i, (s, d) in enumerate(pairs):
+        if s.numel() != d.numel():
+            raise ValueError("segments are pairs of equal-size tensors")
+        srcs[i] = _dev(s, dtype, "src").value
+        dsts[i] = _dev(d, dtype, "dst").value
+        numel[i] = s.numel()
+    _check("sml_copy_segments_typed", lib().sml_copy_segments_typed(
+        ctypes.cast(srcs, ctypes.c_void_p), ctypes.cast(dsts, ctypes.c_void_p), ctypes.cast(numel, ctypes.c_void_p),
+        k, dt, flags, _stream(stream, pairs[0][0] if pairs else None)))
 
 
 def packet_burst(x, out, packet_numel: int, num_workers: int, batch_num_ltus: int, recv_exps, pkt_ids,
