@@ -195,7 +195,12 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
  *     below the normal range -> fp16 denormals, NaN -> a NaN of T).  The planes
  *     are the FLOAT32 ones: int32 payload words and one int8 exponent per
  *     packet of P elements, B = ceil(numel / P) whatever the element size.
- *   SML_FLOAT32: forwards to the untyped entry point (same kernels, same bits).
+ *   SML_FLOAT32: the untyped entry point, exactly.  No check of the typed
+ *     function's own comes before the fp32 twin's, so for every argument
+ *     list — several faults at once included — the call returns the status,
+ *     runs the kernels and writes the bits of its fp32 twin.  This holds for
+ *     every sml_*_typed entry point of this header (the batch, the frames and
+ *     sml_copy_segments_typed among them).
  *   SML_INT32 (or any other value): SML_ERR_UNSUPPORTED.
  * Typed buffers of a 16-bit type need 2-byte alignment only (a slice starts
  * at any element) and no byte outside [ptr, ptr + 2 * numel) is touched;

@@ -70,10 +70,12 @@ using namespace sml;
 
 extern "C" {
 
+// SML_FLOAT32 is forwarded before any check made here, so the fp32 entry
+// point's own checks, in its own order, decide the status (switchml_hip.h).
 sml_status_t sml_exponents_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel, uint32_t packet_numel,
                                  int8_t* d_exps, void* stream) {
-    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (data_type == SML_FLOAT32) return sml_exponents(static_cast<const float*>(d_in), numel, packet_numel, d_exps, stream);
+    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (!is_half(data_type)) return SML_ERR_UNSUPPORTED;
     if (numel && !d_exps) return SML_ERR_INVALID_ARG;
     return quantize_common_h(d_in, data_type, numel, packet_numel, 1, nullptr, nullptr, d_exps, 0, stream);
@@ -82,10 +84,10 @@ sml_status_t sml_exponents_typed(const void* d_in, sml_data_type_t data_type, ui
 sml_status_t sml_quantize_pack_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
                                      uint32_t packet_numel, uint16_t num_workers, const int8_t* d_global_exps,
                                      int32_t* d_payload, int8_t* d_exps_out, uint32_t flags, void* stream) {
-    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (data_type == SML_FLOAT32)
         return sml_quantize_pack(static_cast<const float*>(d_in), numel, packet_numel, num_workers, d_global_exps,
                                  d_payload, d_exps_out, flags, stream);
+    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (!is_half(data_type)) return SML_ERR_UNSUPPORTED;
     if (num_workers == 0) return SML_ERR_INVALID_ARG;
     if (numel && !d_payload) return SML_ERR_INVALID_ARG;
@@ -97,10 +99,10 @@ sml_status_t sml_quantize_pack_typed(const void* d_in, sml_data_type_t data_type
 sml_status_t sml_dequantize_typed(const int32_t* d_payload, const int8_t* d_exps, uint64_t numel,
                                   uint32_t packet_numel, uint16_t num_workers, void* d_out,
                                   sml_data_type_t data_type, uint32_t flags, void* stream) {
-    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (data_type == SML_FLOAT32)
         return sml_dequantize(d_payload, d_exps, numel, packet_numel, num_workers, static_cast<float*>(d_out), flags,
                               stream);
+    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (!is_half(data_type)) return SML_ERR_UNSUPPORTED;
     return plane_dequantize<ElemHalf, kHU>(d_payload, d_exps, numel, packet_numel, num_workers,
                                            static_cast<uint16_t*>(d_out), data_type == SML_FLOAT16, kHU, flags,
@@ -110,10 +112,10 @@ sml_status_t sml_dequantize_typed(const int32_t* d_payload, const int8_t* d_exps
 sml_status_t sml_roundtrip_loopback_typed(const void* d_in, void* d_out, sml_data_type_t data_type, uint64_t numel,
                                           uint32_t packet_numel, uint16_t num_workers, int32_t* d_payload,
                                           int8_t* d_exps_out, uint32_t flags, void* stream) {
-    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (data_type == SML_FLOAT32)
         return sml_roundtrip_loopback(static_cast<const float*>(d_in), static_cast<float*>(d_out), numel, packet_numel,
                                       num_workers, d_payload, d_exps_out, flags, stream);
+    if (!valid_packet(packet_numel)) return SML_ERR_UNSUPPORTED;
     if (!is_half(data_type)) return SML_ERR_UNSUPPORTED;
     return plane_roundtrip<ElemHalf, kHU>(static_cast<const uint16_t*>(d_in), static_cast<uint16_t*>(d_out),
                                           data_type == SML_FLOAT16, kHU, numel, packet_numel, num_workers, d_payload,

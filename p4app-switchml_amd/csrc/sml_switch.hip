@@ -203,16 +203,31 @@ struct CopyOp {
 // The in-node switch's multicast: the W workers' shards gathered in ONE
 // launch.  Copied one after another, each shard would come over one peer's
 // xGMI link at a time; here the tiles are dealt round-robin over the
-// segments in groups of kSegGroup (64 KiB of words), so every resident wave
+// segments in groups of kSegGroup (16 Ki elements), so every resident wave
 // set reads from all W peers — all links at once — while each group stays a
 // contiguous run.  Group g of the launch: segment g % nseg, that segment's
 // group g / nseg (idle once the segment is done: shards differ by at most one
 // block's words).
+//
+// T is the element as the copy sees it — the bits are copied, so uint32_t
+// serves FLOAT32 and INT32 (sml_copy_segments) and uint16_t serves FLOAT16 and
+// BFLOAT16 (sml_copy_segments_typed).  Both sides are aligned to sizeof(T)
+// only, independently: a 16-bit shard ends on an odd element and lands in a
+// tensor slice that starts at any element.  Full tiles of kTileElems elements
+// move one vector of 4 elements per lane per slice through a type declared
+// sizeof(T)-aligned (gfx950's unaligned-access mode keeps it one
+// global_load_dwordx4 / dwordx2 and one store of the same width), the last
+// partial tile goes element by element.  So a 16-bit lane moves 8 bytes, the
+// 16-bit plane kernels' access (h4a): a build with 16 (8 elements per lane:
+// dwordx4, 80 VGPRs) was not faster beyond the rounds' ranges on 8 segments of
+// 2 Mi elements at an odd destination (profiles/half/bench_half_xgmi.json,
+// DESIGN.md §11).
 constexpr uint32_t kSegGroup = 16;   // tiles per group
 
+template <class T>
 struct SegCopyArgs {
-    const uint32_t* src[SML_MAX_SWITCH_WORKERS];
-    uint32_t* dst[SML_MAX_SWITCH_WORKERS];
+    const T* src[SML_MAX_SWITCH_WORKERS];
+    T* dst[SML_MAX_SWITCH_WORKERS];
     uint64_t n[SML_MAX_SWITCH_WORKERS];
     uint32_t nseg;
     uint64_t ntiles;        // nseg x (the largest segment's groups) x kSegGroup
@@ -220,7 +235,9 @@ struct SegCopyArgs {
     uint32_t flags;
 };
 
-__global__ __launch_bounds__(kBlockThreads) void k_copy_segments(SegCopyArgs a) {
+template <class T>
+__global__ __launch_bounds__(kBlockThreads) void k_copy_segments(SegCopyArgs<T> a) {
+    typedef T vec __attribute__((ext_vector_type(4), aligned(sizeof(T))));
     acquire_peer_planes(a.flags);
     const int lane = threadIdx.x & (kWave - 1);
     const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
@@ -230,15 +247,15 @@ __global__ __launch_bounds__(kBlockThreads) void k_copy_segments(SegCopyArgs a) 
         const uint64_t base = ((g / a.nseg) * kSegGroup + t % kSegGroup) * (uint64_t)kTileElems;
         const uint64_t n = a.n[s];
         if (base >= n) continue;
-        const uint32_t* in = a.src[s];
-        uint32_t* out = a.dst[s];
+        const T* in = a.src[s];
+        T* out = a.dst[s];
         if (base + kTileElems <= n) {
-            u4a v[kU];
+            vec v[kU];
 #pragma unroll
             for (int u = 0; u < kU; u++)
-                v[u] = __builtin_nontemporal_load(reinterpret_cast<const u4a*>(in + base + (u * kWave + lane) * 4));
+                v[u] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(in + base + (u * kWave + lane) * 4));
 #pragma unroll
-            for (int u = 0; u < kU; u++) *reinterpret_cast<u4a*>(out + base + (u * kWave + lane) * 4) = v[u];
+            for (int u = 0; u < kU; u++) *reinterpret_cast<vec*>(out + base + (u * kWave + lane) * 4) = v[u];
         } else {
 #pragma unroll
             for (int u = 0; u < kU; u++)
@@ -251,63 +268,33 @@ __global__ __launch_bounds__(kBlockThreads) void k_copy_segments(SegCopyArgs a) 
     }
 }
 
-// The multicast of a FLOAT16 / BFLOAT16 slice (sml_copy_segments_typed): the
-// same deal of tiles over the segments, on 2-byte elements.  A 16-bit shard
-// ends on an odd element and lands in a tensor slice that starts at any
-// element, so both sides are 2-byte aligned only, independently: full tiles
-// move one vector of kSegVec16 elements per lane per slice through a type
-// declared 2-byte aligned (gfx950's unaligned-access mode keeps it one
-// global_load_dwordx2 and one global_store_dwordx2), the last partial tile
-// goes element by element.  The bits are copied, so one instance serves both
-// types.  8 bytes per lane, the 16-bit plane kernels' access (h4a): a build
-// with 16 (kSegVec16 = 8: dwordx4, 80 VGPRs) was not faster beyond the
-// rounds' ranges on 8 segments of 2 Mi elements at an odd destination
-// (profiles/half/bench_half_xgmi.json).
-constexpr int kSegVec16 = 4;   // elements per lane per slice
-constexpr int kSegTile16 = kWave * kSegVec16 * kU;   // 1024
-typedef uint16_t hva __attribute__((ext_vector_type(kSegVec16), aligned(2)));
-
-struct SegCopy16Args {
-    const uint16_t* src[SML_MAX_SWITCH_WORKERS];
-    uint16_t* dst[SML_MAX_SWITCH_WORKERS];
-    uint64_t n[SML_MAX_SWITCH_WORKERS];
-    uint32_t nseg;
-    uint64_t ntiles;        // nseg x (the largest segment's groups) x kSegGroup
-    uint32_t xcd;
-    uint32_t flags;
-};
-
-__global__ __launch_bounds__(kBlockThreads) void k_copy_segments16(SegCopy16Args a) {
-    acquire_peer_planes(a.flags);
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
-    for (uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index(); t < a.ntiles; t += nwaves) {
-        const uint64_t g = t / kSegGroup;
-        const uint32_t s = (uint32_t)(g % a.nseg);
-        const uint64_t base = ((g / a.nseg) * kSegGroup + t % kSegGroup) * (uint64_t)kSegTile16;
-        const uint64_t n = a.n[s];
-        if (base >= n) continue;
-        const uint16_t* in = a.src[s];
-        uint16_t* out = a.dst[s];
-        if (base + kSegTile16 <= n) {
-            hva v[kU];
-#pragma unroll
-            for (int u = 0; u < kU; u++)
-                v[u] = __builtin_nontemporal_load(
-                    reinterpret_cast<const hva*>(in + base + (u * kWave + lane) * kSegVec16));
-#pragma unroll
-            for (int u = 0; u < kU; u++)
-                *reinterpret_cast<hva*>(out + base + (u * kWave + lane) * kSegVec16) = v[u];
-        } else {
-#pragma unroll
-            for (int u = 0; u < kU; u++)
-#pragma unroll
-                for (int j = 0; j < kSegVec16; j++) {
-                    const uint64_t idx = base + (uint64_t)(u * kWave + lane) * kSegVec16 + j;
-                    if (idx < n) out[idx] = in[idx];
-                }
-        }
+// The host half of both entry points: n[i] elements of T per segment.
+template <class T>
+static sml_status_t copy_segments(const void* const* d_srcs, void* const* d_dsts, const uint64_t* n,
+                                  uint32_t num_segments, uint32_t flags, void* stream) {
+    if (num_segments == 0) return SML_OK;
+    if (!d_srcs || !d_dsts || !n || num_segments > SML_MAX_SWITCH_WORKERS) return SML_ERR_INVALID_ARG;
+    SegCopyArgs<T> a;
+    a.nseg = 0;
+    uint64_t groups = 0;
+    const uint64_t ge = (uint64_t)kSegGroup * kTileElems;   // elements per group
+    for (uint32_t i = 0; i < num_segments; i++) {
+        if (n[i] == 0) continue;                            // empty segments touch nothing
+        if (!d_srcs[i] || !d_dsts[i] || (((uintptr_t)d_srcs[i] | (uintptr_t)d_dsts[i]) & (sizeof(T) - 1)))
+            return SML_ERR_INVALID_ARG;
+        a.src[a.nseg] = static_cast<const T*>(d_srcs[i]);
+        a.dst[a.nseg] = static_cast<T*>(d_dsts[i]);
+        a.n[a.nseg] = n[i];
+        const uint64_t gi = (n[i] + ge - 1) / ge;
+        groups = gi > groups ? gi : groups;
+        a.nseg++;
     }
+    if (a.nseg == 0) return SML_OK;
+    a.ntiles = (uint64_t)a.nseg * groups * kSegGroup;
+    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
+    a.flags = flags & SML_FLAG_PEER_PLANES;
+    k_copy_segments<T><<<grid_for_tiles(a.ntiles), kBlockThreads, 0, (hipStream_t)stream>>>(a);
+    return launch_check();
 }
 
 // ncclUint8 buckets (the CollNet plugin, switchml_plugin.cc:318-337 and
@@ -456,58 +443,15 @@ sml_status_t sml_narrow_i32_u8(const int32_t* d_in, uint8_t* d_out, uint64_t n, 
 
 sml_status_t sml_copy_segments(const void* const* d_srcs, void* const* d_dsts, const uint64_t* num_words,
                                uint32_t num_segments, uint32_t flags, void* stream) {
-    if (num_segments == 0) return SML_OK;
-    if (!d_srcs || !d_dsts || !num_words || num_segments > SML_MAX_SWITCH_WORKERS) return SML_ERR_INVALID_ARG;
-    SegCopyArgs a;
-    a.nseg = 0;
-    uint64_t groups = 0;
-    const uint64_t gw = (uint64_t)kSegGroup * kTileElems;   // words per group
-    for (uint32_t i = 0; i < num_segments; i++) {
-        if (num_words[i] == 0) continue;                    // empty segments touch nothing
-        if (!d_srcs[i] || !d_dsts[i] || !aligned4(d_srcs[i]) || !aligned4(d_dsts[i])) return SML_ERR_INVALID_ARG;
-        a.src[a.nseg] = static_cast<const uint32_t*>(d_srcs[i]);
-        a.dst[a.nseg] = static_cast<uint32_t*>(d_dsts[i]);
-        a.n[a.nseg] = num_words[i];
-        const uint64_t gi = (num_words[i] + gw - 1) / gw;
-        groups = gi > groups ? gi : groups;
-        a.nseg++;
-    }
-    if (a.nseg == 0) return SML_OK;
-    a.ntiles = (uint64_t)a.nseg * groups * kSegGroup;
-    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
-    a.flags = flags & SML_FLAG_PEER_PLANES;
-    k_copy_segments<<<grid_for_tiles(a.ntiles), kBlockThreads, 0, (hipStream_t)stream>>>(a);
-    return launch_check();
+    return copy_segments<uint32_t>(d_srcs, d_dsts, num_words, num_segments, flags, stream);
 }
 
 sml_status_t sml_copy_segments_typed(const void* const* d_srcs, void* const* d_dsts, const uint64_t* numel,
                                      uint32_t num_segments, sml_data_type_t data_type, uint32_t flags, void* stream) {
     if (data_type == SML_FLOAT32 || data_type == SML_INT32)
-        return sml_copy_segments(d_srcs, d_dsts, numel, num_segments, flags, stream);
+        return copy_segments<uint32_t>(d_srcs, d_dsts, numel, num_segments, flags, stream);
     if (!is_half(data_type)) return SML_ERR_UNSUPPORTED;
-    if (num_segments == 0) return SML_OK;
-    if (!d_srcs || !d_dsts || !numel || num_segments > SML_MAX_SWITCH_WORKERS) return SML_ERR_INVALID_ARG;
-    SegCopy16Args a;
-    a.nseg = 0;
-    uint64_t groups = 0;
-    const uint64_t ge = (uint64_t)kSegGroup * kSegTile16;   // elements per group
-    for (uint32_t i = 0; i < num_segments; i++) {
-        if (numel[i] == 0) continue;                        // empty segments touch nothing
-        if (!d_srcs[i] || !d_dsts[i] || ((uintptr_t)d_srcs[i] & 1u) || ((uintptr_t)d_dsts[i] & 1u))
-            return SML_ERR_INVALID_ARG;
-        a.src[a.nseg] = static_cast<const uint16_t*>(d_srcs[i]);
-        a.dst[a.nseg] = static_cast<uint16_t*>(d_dsts[i]);
-        a.n[a.nseg] = numel[i];
-        const uint64_t gi = (numel[i] + ge - 1) / ge;
-        groups = gi > groups ? gi : groups;
-        a.nseg++;
-    }
-    if (a.nseg == 0) return SML_OK;
-    a.ntiles = (uint64_t)a.nseg * groups * kSegGroup;
-    a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
-    a.flags = flags & SML_FLAG_PEER_PLANES;
-    k_copy_segments16<<<grid_for_tiles(a.ntiles), kBlockThreads, 0, (hipStream_t)stream>>>(a);
-    return launch_check();
+    return copy_segments<uint16_t>(d_srcs, d_dsts, numel, num_segments, flags, stream);
 }
 
 sml_status_t sml_release_to_peers(void* stream) {

@@ -97,9 +97,11 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     u64, u32, u16, i32, vp = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_int, ctypes.c_void_p
     L.sml_abi_version.restype = i32
+    L.sml_abi_version.argtypes = []
     L.sml_status_string.restype = ctypes.c_char_p
     L.sml_status_string.argtypes = [i32]
     L.sml_last_error.restype = ctypes.c_char_p
+    L.sml_last_error.argtypes = []
     L.sml_num_blocks.restype = u64
     L.sml_num_blocks.argtypes = [u64, u32]
     L.sml_scale_lut.restype = i32
@@ -177,6 +179,12 @@ def lib():
     L.sml_copy_segments_typed.argtypes = [vp, vp, vp, u32, i32, u32, vp]
     L.sml_switch_exps.restype = i32
     L.sml_switch_exps.argtypes = [vp, u16, u64, vp, u32, vp]
+    L.sml_copy_words.restype = i32
+    L.sml_copy_words.argtypes = [vp, vp, u64, vp]
+    L.sml_widen_u8_i32.restype = i32
+    L.sml_widen_u8_i32.argtypes = [vp, vp, u64, vp]
+    L.sml_narrow_i32_u8.restype = i32
+    L.sml_narrow_i32_u8.argtypes = [vp, vp, u64, vp]
     L.sml_release_to_peers.restype = i32
     L.sml_release_to_peers.argtypes = [vp]
     L.sml_preprocess_burst.restype = i32
@@ -198,6 +206,7 @@ def lib():
     L.sml_burst_server_inject_unanswered.restype = i32
     L.sml_burst_server_inject_unanswered.argtypes = [vp, u32, ctypes.POINTER(PacketBurst)]
     L.sml_ipc_handle_bytes.restype = u32
+    L.sml_ipc_handle_bytes.argtypes = []
     L.sml_ipc_get_handle.restype = i32
     L.sml_ipc_get_handle.argtypes = [vp, vp, ctypes.POINTER(u64)]
     L.sml_ipc_open_handle.restype = i32
@@ -338,12 +347,8 @@ def exponents(x, packet_numel: int = 256, out=None, stream=None):
     if out is None:
         out = torch.empty(B, dtype=torch.int8, device=x.device)
     dt = _float_type(x.dtype, "x")
-    if dt != FLOAT32:
-        _check("sml_exponents_typed", lib().sml_exponents_typed(
-            _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, _dev(out, torch.int8, "exps"), _stream(stream, x)))
-        return out
-    _check("sml_exponents", lib().sml_exponents(_dev(x, torch.float32, "x"), x.numel(), packet_numel,
-                                                _dev(out, torch.int8, "exps"), _stream(stream, x)))
+    _check("sml_exponents_typed", lib().sml_exponents_typed(
+        _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, _dev(out, torch.int8, "exps"), _stream(stream, x)))
     return out
 
 
@@ -361,20 +366,15 @@ def quantize_pack(x, packet_numel: int = 256, num_workers: int = 1, global_exps=
     g = None if global_exps is None else _dev(global_exps, torch.int8, "global_exps")
     e = None if exps_out is None else _dev(exps_out, torch.int8, "exps_out")
     dt = _float_type(x.dtype, "x")
-    if dt != FLOAT32:
-        _check("sml_quantize_pack_typed", lib().sml_quantize_pack_typed(
-            _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, num_workers, g,
-            _dev(payload, torch.int32, "payload"), e, flags, _stream(stream, x)))
-    else:
-        _check("sml_quantize_pack", lib().sml_quantize_pack(
-            _dev(x, torch.float32, "x"), x.numel(), packet_numel, num_workers, g,
-            _dev(payload, torch.int32, "payload"), e, flags, _stream(stream, x)))
+    _check("sml_quantize_pack_typed", lib().sml_quantize_pack_typed(
+        _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, num_workers, g,
+        _dev(payload, torch.int32, "payload"), e, flags, _stream(stream, x)))
     return payload, (global_exps if global_exps is not None else exps_out)
 
 
 def quantize_pack_launcher(x, packet_numel: int, num_workers: int, payload, exps_out=None, global_exps=None,
                            flags: int = 0, stream=None):
-    """A zero-argument callable that launches sml_quantize_pack on these
+    """A zero-argument callable that launches sml_quantize_pack_typed on these
     tensors: every argument checked and converted once, so a loop over the
     same bucket (a training step's gradient bucket, the bench's steps) pays
     one C call per launch instead of the wrapper's tensor checks.  The
@@ -390,15 +390,12 @@ def quantize_pack_launcher(x, packet_numel: int, num_workers: int, payload, exps
             None if global_exps is None else _dev(global_exps, torch.int8, "global_exps"),
             _dev(payload, torch.int32, "payload"),
             None if exps_out is None else _dev(exps_out, torch.int8, "exps_out"), flags, _stream(stream, x))
-    if dt != FLOAT32:
-        name, fn, args = "sml_quantize_pack_typed", lib().sml_quantize_pack_typed, (_dev(x, x.dtype, "x"), dt) + args
-    else:
-        name, fn, args = "sml_quantize_pack", lib().sml_quantize_pack, (_dev(x, torch.float32, "x"),) + args
+    fn, args = lib().sml_quantize_pack_typed, (_dev(x, x.dtype, "x"), dt) + args
 
     def launch():
         s = fn(*args)
         if s != SML_OK:
-            raise SwitchMLError(name, s)
+            raise SwitchMLError("sml_quantize_pack_typed", s)
     return launch
 
 
@@ -412,14 +409,9 @@ def dequantize(payload, exps, numel: int, packet_numel: int = 256, num_workers: 
     elif out_dtype is not None and out.dtype != out_dtype:
         raise TypeError(f"out is {out.dtype}, out_dtype {out_dtype}")
     dt = _float_type(out.dtype, "out")
-    if dt != FLOAT32:
-        _check("sml_dequantize_typed", lib().sml_dequantize_typed(
-            _dev(payload, torch.int32, "payload"), _dev(exps, torch.int8, "exps"), numel, packet_numel,
-            num_workers, _dev(out, out.dtype, "out"), dt, flags, _stream(stream, payload)))
-        return out
-    _check("sml_dequantize", lib().sml_dequantize(
+    _check("sml_dequantize_typed", lib().sml_dequantize_typed(
         _dev(payload, torch.int32, "payload"), _dev(exps, torch.int8, "exps"), numel, packet_numel,
-        num_workers, _dev(out, torch.float32, "out"), flags, _stream(stream, payload)))
+        num_workers, _dev(out, out.dtype, "out"), dt, flags, _stream(stream, payload)))
     return out
 
 
@@ -446,14 +438,9 @@ def roundtrip_loopback(x, packet_numel: int = 256, num_workers: int = 1, out=Non
         out = torch.empty_like(x)
     p = None if payload is None else _dev(payload, torch.int32, "payload")
     e = None if exps_out is None else _dev(exps_out, torch.int8, "exps_out")
-    dt = _float_type(x.dtype, "x")
-    if dt != FLOAT32:   # fp16 / bf16 in, the same type out
-        _check("sml_roundtrip_loopback_typed", lib().sml_roundtrip_loopback_typed(
-            _dev(x, x.dtype, "x"), _dev(out, x.dtype, "out"), dt, x.numel(), packet_numel,
-            num_workers, p, e, flags, _stream(stream, x)))
-        return out
-    _check("sml_roundtrip_loopback", lib().sml_roundtrip_loopback(
-        _dev(x, torch.float32, "x"), _dev(out, torch.float32, "out"), x.numel(), packet_numel,
+    dt = _float_type(x.dtype, "x")   # the same type in and out
+    _check("sml_roundtrip_loopback_typed", lib().sml_roundtrip_loopback_typed(
+        _dev(x, x.dtype, "x"), _dev(out, x.dtype, "out"), dt, x.numel(), packet_numel,
         num_workers, p, e, flags, _stream(stream, x)))
     return out
 
@@ -477,28 +464,20 @@ def roundtrip_loopback_batch(slices, packet_numel: int = 256, num_workers: int =
     list of (x, out) device (or pinned host) tensor pairs, fp32, fp16 or bf16
     (a pair's two dtypes equal, the pairs' dtypes free); slice i gets exactly
     roundtrip_loopback(x_i, out=out_i) — its blocks start at its own first
-    element.  An all-fp32 list is one sml_roundtrip_loopback_batch launch; a
-    list with a 16-bit slice goes whole through
-    sml_roundtrip_loopback_batch_typed (one launch per dtype present)."""
-    torch = _torch()
+    element.  The list goes whole through sml_roundtrip_loopback_batch_typed:
+    one launch per dtype present (an all-fp32 list: the one launch of
+    sml_roundtrip_loopback_batch)."""
     for x, o in slices:
         if x.numel() != o.numel():
             raise ValueError("slice in/out sizes differ")
         if getattr(x, "dtype", None) != getattr(o, "dtype", None):
             raise TypeError(f"slice in/out dtypes differ: {x.dtype}, {o.dtype}")
     st = _stream(stream, slices[0][0]) if slices else None
-    if any(getattr(x, "dtype", None) in (torch.float16, torch.bfloat16) for x, _ in slices):
-        tarr = (TypedSlice * len(slices))()
-        for i, (x, o) in enumerate(slices):
-            dt = _float_type(x.dtype, "x")
-            tarr[i] = TypedSlice(_dev(x, x.dtype, "x").value, _dev(o, x.dtype, "out").value, x.numel(), dt, 0)
-        _check("sml_roundtrip_loopback_batch_typed", lib().sml_roundtrip_loopback_batch_typed(
-            tarr, len(slices), packet_numel, num_workers, flags, st))
-        return
-    arr = (Slice * max(1, len(slices)))()
+    arr = (TypedSlice * max(1, len(slices)))()
     for i, (x, o) in enumerate(slices):
-        arr[i] = Slice(_dev(x, torch.float32, "x").value, _dev(o, torch.float32, "out").value, x.numel())
-    _check("sml_roundtrip_loopback_batch", lib().sml_roundtrip_loopback_batch(
+        dt = _float_type(getattr(x, "dtype", None), "x")
+        arr[i] = TypedSlice(_dev(x, x.dtype, "x").value, _dev(o, x.dtype, "out").value, x.numel(), dt, 0)
+    _check("sml_roundtrip_loopback_batch_typed", lib().sml_roundtrip_loopback_batch_typed(
         arr, len(slices), packet_numel, num_workers, flags, st))
 
 
@@ -540,21 +519,30 @@ def switch_aggregate(payloads, exps=None, numel: int | None = None, packet_numel
     pp = (ctypes.c_void_p * W)(*[_dev(p, torch.int32, "payloads[w]").value if isinstance(p, torch.Tensor)
                                  else p.data_ptr() for p in payloads])
     ep = None if exps is None else (ctypes.c_void_p * W)(*[_dev(e, torch.int8, "exps[w]").value for e in exps])
-    if dt != FLOAT32:
-        _check("sml_switch_aggregate_typed", lib().sml_switch_aggregate_typed(
-            ctypes.cast(pp, ctypes.c_void_p), None if ep is None else ctypes.cast(ep, ctypes.c_void_p), W, numel,
-            packet_numel,
-            None if payload_out is None else _dev(payload_out, torch.int32, "payload_out"),
-            None if exps_out is None else _dev(exps_out, torch.int8, "exps_out"),
-            _dev(out, out.dtype, "out"), dt, flags, _stream(stream, payloads[0])))
-        return out
-    _check("sml_switch_aggregate", lib().sml_switch_aggregate(
+    _check("sml_switch_aggregate_typed", lib().sml_switch_aggregate_typed(
         ctypes.cast(pp, ctypes.c_void_p), None if ep is None else ctypes.cast(ep, ctypes.c_void_p), W, numel,
         packet_numel,
         None if payload_out is None else _dev(payload_out, torch.int32, "payload_out"),
         None if exps_out is None else _dev(exps_out, torch.int8, "exps_out"),
-        None if out is None else _dev(out, torch.float32, "out"), flags, _stream(stream, payloads[0])))
+        None if out is None else _dev(out, out.dtype, "out"), dt, flags, _stream(stream, payloads[0])))
     return out
+
+
+def _segment_tables(pairs, dtype=None):
+    """The three tables of a segment copy — sources, destinations, element
+    counts, as void* — from (src, dst) tensor pairs of equal numel, all of
+    `dtype` (None: any 32-bit dtypes, each tensor its own)."""
+    k = len(pairs)
+    srcs = (ctypes.c_void_p * max(1, k))()
+    dsts = (ctypes.c_void_p * max(1, k))()
+    numel = (ctypes.c_uint64 * max(1, k))()
+    for i, (s, d) in enumerate(pairs):
+        if s.numel() != d.numel() or (dtype is None and (s.element_size() != 4 or d.element_size() != 4)):
+            raise ValueError("segments are pairs of equal-size " + ("32-bit tensors" if dtype is None else "tensors"))
+        srcs[i] = _dev(s, dtype or s.dtype, "src").value
+        dsts[i] = _dev(d, dtype or d.dtype, "dst").value
+        numel[i] = s.numel()
+    return tuple(ctypes.cast(t, ctypes.c_void_p) for t in (srcs, dsts, numel))
 
 
 def copy_segments(pairs, flags: int = 0, stream=None):
@@ -562,22 +550,11 @@ def copy_segments(pairs, flags: int = 0, stream=None):
     numel; CUDA or pinned host) copied in ONE launch, the tiles dealt
     round-robin over the pairs (the in-node switch's multicast).
     flags = FLAG_PEER_PLANES when sources were written by other GPUs."""
-    torch = _torch()
-    k = len(pairs)
-    if k > MAX_SWITCH_WORKERS:
+    if len(pairs) > MAX_SWITCH_WORKERS:
         raise ValueError(f"at most {MAX_SWITCH_WORKERS} segments")
-    srcs = (ctypes.c_void_p * max(1, k))()
-    dsts = (ctypes.c_void_p * max(1, k))()
-    words = (ctypes.c_uint64 * max(1, k))()
-    for i, (s, d) in enumerate(pairs):
-        if s.numel() != d.numel() or s.element_size() != 4 or d.element_size() != 4:
-            raise ValueError("segments are pairs of equal-size 32-bit tensors")
-        srcs[i] = _dev(s, s.dtype, "src").value
-        dsts[i] = _dev(d, d.dtype, "dst").value
-        words[i] = s.numel()
+    srcs, dsts, words = _segment_tables(pairs)
     _check("sml_copy_segments", lib().sml_copy_segments(
-        ctypes.cast(srcs, ctypes.c_void_p), ctypes.cast(dsts, ctypes.c_void_p), ctypes.cast(words, ctypes.c_void_p),
-        k, flags, _stream(stream, pairs[0][0] if pairs else None)))
+        srcs, dsts, words, len(pairs), flags, _stream(stream, pairs[0][0] if pairs else None)))
 
 
 def copy_segments_typed(pairs, flags: int = 0, stream=None):
@@ -595,18 +572,9 @@ def copy_segments_typed(pairs, flags: int = 0, stream=None):
         raise TypeError(f"segments are tensors of one dtype, got {sorted(map(str, dtypes))}")
     dtype = dtypes.pop() if dtypes else torch.float32
     dt = INT32 if dtype == torch.int32 else _float_type(dtype, "segments")
-    srcs = (ctypes.c_void_p * max(1, k))()
-    dsts = (ctypes.c_void_p * max(1, k))()
-    numel = (ctypes.c_uint64 * max(1, k))()
-    for i, (s, d) in enumerate(pairs):
-        if s.numel() != d.numel():
-            raise ValueError("segments are pairs of equal-size tensors")
-        srcs[i] = _dev(s, dtype, "src").value
-        dsts[i] = _dev(d, dtype, "dst").value
-        numel[i] = s.numel()
+    srcs, dsts, numel = _segment_tables(pairs, dtype)
     _check("sml_copy_segments_typed", lib().sml_copy_segments_typed(
-        ctypes.cast(srcs, ctypes.c_void_p), ctypes.cast(dsts, ctypes.c_void_p), ctypes.cast(numel, ctypes.c_void_p),
-        k, dt, flags, _stream(stream, pairs[0][0] if pairs else None)))
+        srcs, dsts, numel, k, dt, flags, _stream(stream, pairs[0][0] if pairs else None)))
 
 
 def packet_burst(x, out, packet_numel: int, num_workers: int, batch_num_ltus: int, recv_exps, pkt_ids,
@@ -726,13 +694,8 @@ def quantize_pack_frames(x, params: FrameParams, packet_numel: int = 256, num_wo
         frames = torch.empty((B + b) * stride, dtype=torch.uint8, device=x.device)
     g = None if global_exps is None else _dev(global_exps, torch.int8, "global_exps")
     dt = _float_type(x.dtype, "x")
-    if dt != FLOAT32:
-        _check("sml_quantize_pack_frames_typed", lib().sml_quantize_pack_frames_typed(
-            _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, num_workers, g, batch_max,
-            ctypes.byref(params), _dev(frames, torch.uint8, "frames"), stride, _stream(stream, x)))
-        return frames
-    _check("sml_quantize_pack_frames", lib().sml_quantize_pack_frames(
-        _dev(x, torch.float32, "x"), x.numel(), packet_numel, num_workers, g, batch_max,
+    _check("sml_quantize_pack_frames_typed", lib().sml_quantize_pack_frames_typed(
+        _dev(x, x.dtype, "x"), dt, x.numel(), packet_numel, num_workers, g, batch_max,
         ctypes.byref(params), _dev(frames, torch.uint8, "frames"), stride, _stream(stream, x)))
     return frames
 
@@ -776,16 +739,10 @@ def dequantize_frames(frames, num_frames: int, rx: RxSlice, num_workers: int = 1
     torch = _torch()
     stride = stride or frame_bytes(rx.packet_numel)
     dt = _float_type(rx.out.dtype, "rx.out")
-    if dt != FLOAT32:
-        _check("sml_dequantize_frames_typed", lib().sml_dequantize_frames_typed(
-            _dev(frames, torch.uint8, "frames"), num_frames, stride, rx.numel, rx.packet_numel, num_workers,
-            rx.batch_max, job_id, _dev(rx.exps, torch.int8, "exps"), _dev(rx.state, torch.int64, "state"),
-            _dev(rx.out, rx.out.dtype, "out"), dt, _dev(rx.counts, torch.int64, "counts"), _stream(stream, rx.out)))
-        return rx.out
-    _check("sml_dequantize_frames", lib().sml_dequantize_frames(
+    _check("sml_dequantize_frames_typed", lib().sml_dequantize_frames_typed(
         _dev(frames, torch.uint8, "frames"), num_frames, stride, rx.numel, rx.packet_numel, num_workers,
         rx.batch_max, job_id, _dev(rx.exps, torch.int8, "exps"), _dev(rx.state, torch.int64, "state"),
-        _dev(rx.out, torch.float32, "out"), _dev(rx.counts, torch.int64, "counts"), _stream(stream, rx.out)))
+        _dev(rx.out, rx.out.dtype, "out"), dt, _dev(rx.counts, torch.int64, "counts"), _stream(stream, rx.out)))
     return rx.out
 
 

@@ -3,6 +3,7 @@ exports every entry point include/switchml_hip.h declares, and its host-only
 entry points (geometry, scale LUT, argument validation) behave — validation
 returns before any HIP call, so these run without a device."""
 import ctypes
+import re
 
 import numpy as np
 import pytest
@@ -23,6 +24,35 @@ def test_exports_every_header_symbol(sw):
     L = sw.lib()
     missing = [s for s in syms if not hasattr(L, s)]
     assert not missing, missing
+
+
+def header_prototypes(path):
+    """{function: (return type, parameter count)} of a C-ABI header, comments
+    stripped as header_symbols does; `(void)` counts 0."""
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w ]*?\**)\s*\b(sml_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = params.strip()
+        protos[name] = (" ".join(ret.split()), 0 if params in ("", "void") else params.count(",") + 1)
+    return protos
+
+
+def test_every_header_function_has_a_ctypes_prototype(sw):
+    """lib() declares restype and argtypes for every function of the header:
+    without argtypes ctypes passes a Python int as a C int and truncates a
+    pointer.  An unset restype reads as c_int, which a set one may equal, so
+    restype is held against the header's return type instead."""
+    protos = header_prototypes(sw.HEADER_PATH)
+    assert sorted(protos) == sw.header_symbols()
+    restype = {"sml_status_t": ctypes.c_int, "int": ctypes.c_int, "uint32_t": ctypes.c_uint32,
+               "uint64_t": ctypes.c_uint64, "const char*": ctypes.c_char_p}
+    L = sw.lib()
+    bad = []
+    for name, (ret, nparams) in sorted(protos.items()):
+        fn = getattr(L, name)
+        if fn.argtypes is None or len(fn.argtypes) != nparams or fn.restype is not restype[ret]:
+            bad.append((name, ret, nparams, fn.restype, fn.argtypes))
+    assert not bad, bad
 
 
 def test_abi_version_and_status_strings(sw):

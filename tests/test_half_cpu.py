@@ -92,6 +92,108 @@ def test_typed_validation_without_gpu(sw, name, dt):
     assert call(None, dt, 0, 100, W, None, None) == sw.SML_ERR_UNSUPPORTED
 
 
+# fp32 entry point -> where its typed twin takes the sml_data_type_t
+TWIN_TYPE_ARG = {"sml_exponents": 1, "sml_quantize_pack": 1, "sml_dequantize": 6, "sml_roundtrip_loopback": 2,
+                 "sml_quantize_pack_frames": 1, "sml_dequantize_frames": 11, "sml_switch_aggregate": 8,
+                 "sml_copy_segments": 4}
+
+
+class RecordingLib:
+    """The library, noting every call of an fp32 entry point that has a typed twin."""
+
+    def __init__(self, L, calls):
+        self._L, self._calls = L, calls
+
+    def __getattr__(self, name):
+        fn = getattr(self._L, name)
+        if name not in TWIN_TYPE_ARG:
+            return fn
+
+        def call(*args):
+            self._calls.append((name, args))
+            return fn(*args)
+        return call
+
+
+class RecordingModule:
+    """switchml_amd with lib() recording (what the C-ABI tests take as `sw`)."""
+
+    def __init__(self, sw, calls):
+        self._sw, self._lib = sw, RecordingLib(sw.lib(), calls)
+
+    def lib(self):
+        return self._lib
+
+    def __getattr__(self, name):
+        return getattr(self._sw, name)
+
+
+def test_typed_float32_returns_what_its_fp32_twin_returns(sw):
+    """A typed entry point given SML_FLOAT32 is its fp32 twin (switchml_hip.h):
+    equal status for every argument list the C-ABI validation tests send to an
+    fp32 entry point — lists where two checks fail at once included, such as a
+    bad packet size with num_workers == 0 — and for a grid of bad tables,
+    worker counts and planes on the switch's aggregate and segment copy.
+    Every check returns before a HIP call, so no device is needed."""
+    import test_capi_cpu as capi
+    L = sw.lib()
+    calls = []
+    rec = RecordingModule(sw, calls)
+    capi.test_argument_validation_without_gpu(rec)
+    capi.test_frames_and_rdma_validation_without_gpu(rec)
+    capi.test_rx_frames_validation_without_gpu(rec)
+    assert {name for name, _ in calls} == set(TWIN_TYPE_ARG) - {"sml_switch_aggregate", "sml_copy_segments"}
+
+    vp = ctypes.c_void_p
+    backing = (ctypes.c_uint8 * 8192)()
+    base = (ctypes.addressof(backing) + 63) & ~63           # 64-byte aligned
+    out, pay, exps = base, base + 1024, base + 6144
+
+    def table(k, p):
+        return ctypes.cast((vp * k)(*[p] * k), vp)
+
+    # Every list below has a fault or nothing to do, so none reaches a launch:
+    # the one sound combination of each grid is left out.
+    for W in (0, 1, 16, 17):
+        k = max(W, 1)
+        tables = ((table(k, pay), table(k, exps)),              # sound
+                  (None, table(k, exps)), (table(k, pay), None),    # a null table
+                  (table(k, pay + 4), table(k, exps)),              # planes off their 16 bytes
+                  (table(k, None), table(k, exps)))                 # null planes
+        for i, (pp, ep) in enumerate(tables):
+            for P in (256, 100):
+                sound = i == 0 and W in (1, 16) and P == 256
+                # a bucket off its 4 bytes, no output at all, a sound bucket
+                for o in (out + 2, None) + (() if sound else (out,)):
+                    calls.append(("sml_switch_aggregate", (pp, ep, W, 16, P, None, None, o, 0, None)))
+                calls.append(("sml_switch_aggregate", (pp, ep, W, 16, P, pay + 4, None, out, 0, None)))
+                calls.append(("sml_switch_aggregate", (pp, ep, W, 0, P, None, None, None, 0, None)))
+    words = ctypes.cast((ctypes.c_uint64 * 17)(*[4] * 17), vp)
+    empty = ctypes.cast((ctypes.c_uint64 * 17)(), vp)
+    for k in (0, 1, 16, 17):
+        tables = ((table(17, out), table(17, pay)),             # sound
+                  (None, table(17, pay)), (table(17, out), None),   # a null table
+                  (table(17, out + 2), table(17, pay)), (table(17, out), table(17, pay + 1)),   # off their 4 bytes
+                  (table(17, None), table(17, pay)))                # null segments
+        for i, (srcs, dsts) in enumerate(tables):
+            for n in (empty, None) + (() if i == 0 and k in (1, 16) else (words,)):
+                calls.append(("sml_copy_segments", (srcs, dsts, n, k, 0, None)))
+
+    seen = set()
+    for name, args in calls:
+        at = TWIN_TYPE_ARG[name]
+        s32 = getattr(L, name)(*args)
+        st = getattr(L, name + "_typed")(*args[:at], F32, *args[at:])
+        assert st == s32, (name, args, st, s32)
+        assert s32 != sw.SML_ERR_HIP, (name, args)          # a check answered, not the device
+        seen.add((name, s32))
+    # the lists reach every status on both sides of the grid
+    for name in ("sml_switch_aggregate", "sml_copy_segments"):
+        assert {s for n_, s in seen if n_ == name} >= {sw.SML_OK, sw.SML_ERR_INVALID_ARG}
+    assert ("sml_switch_aggregate", sw.SML_ERR_UNSUPPORTED) in seen      # 17 workers, bad P
+    assert ("sml_switch_aggregate", sw.SML_ERR_ALIGNMENT) in seen        # a plane off its 16 bytes
+
+
 def test_client_data_type_sizes_and_wire_geometry():
     """sml_allreduce with data_type 2 / 3 under the bypass PPP: the job
     finishes, and every FIFO slice counts ceil(numel / P) packets (bypass has
