@@ -4,9 +4,13 @@ TEST INFRASTRUCTURE ONLY.  Imported by tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg as the checker / reported CPU baseline.  The
 product path (p4app-switchml_amd/) never imports this module.
 
-Parity status: "parity unpinned" at the bit level — the reference client_lib
-is not buildable here (client_lib/src/common.h:31 needs glog, absent from the
-image).  Pinned by the reference's own 1 % known-answer checks
+Parity status: pinned bit for bit to the compiled reference for the VCL=0
+scalar path, the dummy packet loop and the FIFO split: oracle/ref/ builds the
+reference's client_lib unmodified into oracle/_ref/ (a stand-in glog header is
+all it lacks) and tests/test_oracle_vs_reference.py compares; see the
+ref_* wrappers below and DESIGN.md §3.  Still "parity unpinned": the VCL=1
+rounding, the DPDK frames, the RDMA immediates, the P4 switch arithmetic.
+Also pinned by the reference's own 1 % known-answer checks
 (examples/hello_world/main.cc:58-74, benchmarks/allreduce_benchmark/main.cc:331-399)
 and by hand-derived vectors (tests/golden/).
 
@@ -276,6 +280,158 @@ def unpack_frames_i32(frames: np.ndarray, num_frames: int, stride: int, rx: RxSt
 
 def pool_index(pkt_id, start, shift, mop) -> int:
     return int(lib().orc_pkt_id_to_pool_index(pkt_id, start, shift, mop))
+
+
+# ------------------------------------------------- the compiled reference --
+#
+# oracle/ref/ builds the reference's client library, unmodified, into
+# oracle/_ref/ (git-ignored; present only where the reference checkout is).
+# These wrappers are what tests/test_oracle_vs_reference.py and
+# tests/golden/make_ref_vectors.py hold the oracle to.  Nothing on a GPU path
+# may call them.
+
+_REF_RECIPE = os.path.join(_HERE, "ref")
+_REF_DIR = os.path.join(_HERE, "_ref")
+_REF_LIBS = {False: os.path.join(_REF_DIR, "libsml_ref_ppp.so"),
+             True: os.path.join(_REF_DIR, "libsml_ref_ppp_debug.so")}
+_REF_ALLREDUCE = os.path.join(_REF_DIR, "ref_allreduce")
+_ref_libs = {}
+
+FLOAT32, INT32 = 0, 1
+SENTINEL_WORD = 0xA5C3F00D
+SENTINEL_BYTE = 0x5A
+
+
+def reference_dir() -> str:
+    """Where the reference checkout is looked for (SML_REFERENCE overrides
+    the default, which is also oracle/ref/Makefile's)."""
+    return os.environ.get("SML_REFERENCE", "/root/reference")
+
+
+def reference_checkout_available() -> bool:
+    return os.path.isfile(os.path.join(reference_dir(), "dev_root", "client_lib", "src", "prepostprocessors",
+                                       "cpu_exponent_quantizer_ppp.cc"))
+
+
+def ref_available() -> bool:
+    """True where oracle/_ref/ holds the two libraries and the program."""
+    return all(os.path.isfile(p) for p in (*_REF_LIBS.values(), _REF_ALLREDUCE))
+
+
+def build_ref() -> str:
+    """Compile the reference into oracle/_ref/ with the committed recipe."""
+    subprocess.run(["make", "-s", "-C", _REF_RECIPE, f"REFERENCE={reference_dir()}"], check=True)
+    return _REF_DIR
+
+
+def _ref_lib(debug: bool):
+    debug = bool(debug)
+    if debug not in _ref_libs:
+        L = ctypes.CDLL(_REF_LIBS[debug])
+        u64, vp = ctypes.c_uint64, ctypes.c_void_p
+        L.refppp_create.restype = vp
+        L.refppp_create.argtypes = [ctypes.c_uint16, u64, u64]
+        L.refppp_setup.restype = u64
+        L.refppp_setup.argtypes = [vp, vp, vp, u64, ctypes.c_int]
+        L.refppp_needs_extra_batch.restype = ctypes.c_int
+        L.refppp_needs_extra_batch.argtypes = [vp]
+        L.refppp_pre.argtypes = [vp, u64, vp, vp]
+        L.refppp_post.argtypes = [vp, u64, vp, vp]
+        L.refppp_pre_range.argtypes = [vp, u64, u64, vp, u64, vp, u64]
+        L.refppp_post_range.argtypes = [vp, u64, u64, vp, u64, vp, u64]
+        L.refppp_destroy.argtypes = [vp]
+        _ref_libs[debug] = L
+    return _ref_libs[debug]
+
+
+def ref_packet_stream(x: np.ndarray, P: int, num_workers: int = 1, batch: int = 64, *, debug: bool = False,
+                      global_exps: np.ndarray | None = None, rx_words: np.ndarray | None = None,
+                      aggregate: bool = False) -> dict:
+    """One job slice through the reference's CpuExponentQuantizerPPP, packet by
+    packet, in DummyWorkerThread's call order with in-order delivery.
+
+    x is float32 (FLOAT32 slice) or int32 (INT32 slice).  Every packet gets a
+    buffer of its own, prefilled with SENTINEL_WORD / SENTINEL_BYTE, so what the
+    reference never writes stays visible.  Between send and receive:
+      global_exps[B]  replaces the exponent byte of packets p < B (the switch's
+                      maximum over the workers);
+      rx_words[B*P]   replaces the payload of the main packets (arbitrary
+                      aggregated words); otherwise
+      aggregate       applies the dummy backend's x num_workers to them.
+    Returns dict(B, b, total, tx[total, P] uint32 as sent, tx_extra[total, 2]
+    uint8 as sent, out (dtype of x)).  FLOAT32: packet p >= b carries block
+    p - b, packet p < B the exponent of block p; INT32: total == B, packet p
+    carries block p."""
+    L = _ref_lib(debug)
+    is_f32 = x.dtype == np.float32
+    assert is_f32 or x.dtype == np.int32
+    x = np.ascontiguousarray(x)
+    n = x.size
+    out = np.zeros(n, dtype=x.dtype)
+    h = L.refppp_create(num_workers, P * 4, batch)
+    try:
+        B = int(L.refppp_setup(h, _p(x), _p(out), n, FLOAT32 if is_f32 else INT32))
+        extra = bool(L.refppp_needs_extra_batch(h))
+        b = min(B, batch)
+        total = B + b if extra else B
+        tx = np.full((total, P), SENTINEL_WORD, dtype=np.uint32)
+        tx_extra = np.full((total, 2), SENTINEL_BYTE, dtype=np.uint8)
+        rx = np.empty_like(tx)
+        rx_extra = np.empty_like(tx_extra)
+
+        def send(first, count):
+            if count <= 0:
+                return
+            L.refppp_pre_range(h, first, count, _p(tx[first:]), P * 4, _p(tx_extra[first:]), 2)
+            lo, hi = first, first + count
+            rx[lo:hi] = tx[lo:hi]
+            rx_extra[lo:hi] = tx_extra[lo:hi]
+            if extra and global_exps is not None:
+                k = min(hi, B)
+                if k > lo:
+                    rx_extra[lo:k, 0] = np.asarray(global_exps[lo:k], dtype=np.int8).view(np.uint8)
+            m0 = max(lo, b) if extra else lo           # main packets of the chunk
+            if hi > m0:
+                blk = slice(m0 - (b if extra else 0), hi - (b if extra else 0))
+                if rx_words is not None:
+                    rx[m0:hi] = np.asarray(rx_words, dtype=np.uint32).reshape(B, P)[blk]
+                elif aggregate:
+                    rx[m0:hi] = loopback_aggregate(rx[m0:hi].reshape(-1), num_workers).reshape(-1, P)
+
+        step = max(b, 1)
+        send(0, min(step, total))
+        for first in range(0, total, step):
+            count = min(step, total - first)
+            L.refppp_post_range(h, first, count, _p(rx[first:]), P * 4, _p(rx_extra[first:]), 2)
+            send(first + step, min(step, total - first - step))
+    finally:
+        L.refppp_destroy(h)
+    return dict(B=B, b=b, total=total, tx=tx, tx_extra=tx_extra, out=out)
+
+
+def ref_allreduce(x: np.ndarray, jobs=None, *, P: int = 256, num_workers: int = 1, num_worker_threads: int = 4,
+                  max_outstanding_packets: int = 256, process_packets: bool = True, inplace: bool = False,
+                  timeout: float = 120.0) -> np.ndarray:
+    """The reference's dummy-backend Context in a fresh child process.
+    x: float32 or int32 buffer; jobs: [(offset, numel), ...] all-reduce jobs
+    over parts of it, submitted in that order (default: one job over all of
+    it).  Returns the result buffer (x's dtype; out of place, elements that no
+    job covers are 0)."""
+    import tempfile
+    assert x.dtype in (np.float32, np.int32)
+    x = np.ascontiguousarray(x)
+    if jobs is None:
+        jobs = [(0, x.size)]
+    with tempfile.TemporaryDirectory(prefix="sml_ref_") as d:
+        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        x.tofile(fin)
+        cmd = [_REF_ALLREDUCE, str(num_workers), str(num_worker_threads), str(P), str(max_outstanding_packets),
+               str(int(process_packets)), "f32" if x.dtype == np.float32 else "i32", str(int(inplace)), fin, fout]
+        cmd += [f"{int(o)}:{int(m)}" for o, m in jobs]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+        if r.returncode != 0:
+            raise RuntimeError(f"ref_allreduce failed rc={r.returncode}: {r.stderr[-500:]}")
+        return np.fromfile(fout, dtype=x.dtype, count=x.size)
 
 
 # ------------------------------------------- independent numpy restatement --

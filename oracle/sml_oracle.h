@@ -6,13 +6,14 @@
  * bench.py's cpu_baseline leg may load it, and only as the checker / the
  * reported CPU baseline, never as the measured GPU path.
  *
- * Parity status: the reference client_lib cannot be built in this image
- * (common.h:31 includes <glog/logging.h>; glog is absent and stand-ins are
- * not allowed), so this restatement is pinned only by the reference's own
- * known-answer checks (examples/hello_world/main.cc:58-74 and
- * benchmarks/allreduce_benchmark/main.cc:331-399, both 1 % relative) plus
- * hand-derived vectors from reading ppp.cc.  Bit-level parity with the
- * compiled reference is therefore "parity unpinned" (see DESIGN.md §3).
+ * Parity status: the VCL=0 scalar path, the packet loop and the slice
+ * geometry are held bit for bit to the compiled reference (oracle/ref/ builds
+ * it unmodified with a stand-in glog header; tests/test_oracle_vs_reference.py),
+ * besides the reference's own known-answer checks
+ * (examples/hello_world/main.cc:58-74 and
+ * benchmarks/allreduce_benchmark/main.cc:331-399, both 1 % relative) and
+ * hand-derived vectors.  The VCL=1 rounding, the DPDK frame builder and the
+ * switch arithmetic stay "parity unpinned" (see DESIGN.md §3).
  *
  * All file:line citations are relative to /root/reference/dev_root/client_lib/src/
  * ("ppp.cc" = prepostprocessors/cpu_exponent_quantizer_ppp.cc).

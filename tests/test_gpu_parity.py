@@ -6,8 +6,9 @@ exception is the NaN payload of 0/0 in dequantize (scale 0 from a float
 overflow of W*2^e, ppp.cc:258, times a zero word): x86 yields the default
 NaN 0xffc00000, gfx950 0x7fc00000 — both sides are required to be NaN.
 
-Oracle: oracle/sml_oracle.c (a CPU restatement of ppp.cc; "parity unpinned"
-at the bit level).
+Oracle: oracle/sml_oracle.c (a CPU restatement of ppp.cc, held bit for bit to
+the compiled reference on the CPU: tests/test_oracle_vs_reference.py,
+DESIGN.md §3).
 """
 import numpy as np
 import pytest
