@@ -115,6 +115,28 @@ void HipExponentQuantizerPPP::PostprocessSingle(uint64_t ltu_id, void* entries_p
     postprocess_single(ltu_id, entries_ptr, extra_info);
 }
 
+// Destination for a kernel that writes `bytes` of a packet buffer: launch(dst)
+// with its device address, or (pageable memory, or !in_place) with the staging
+// buffer, then copied out on the stream.  Returns whether the call must sync.
+template <class T, class Launch>
+bool HipExponentQuantizerPPP::write_packet(void* buf, T* stage, size_t bytes, bool in_place, Launch&& launch) {
+    const PointerInfo m = QueryPointer(buf);
+    T* dst = (m.dev && in_place) ? static_cast<T*>(m.dev) : stage;
+    launch(dst);
+    if (dst == stage) hip_ok(hipMemcpyAsync(buf, stage, bytes, hipMemcpyDefault, stream_), "hipMemcpyAsync");
+    return m.host();
+}
+
+// Source for a kernel that reads `bytes` of a packet buffer: its device
+// address, or the staging buffer after a copy in on the stream.
+const int32_t* HipExponentQuantizerPPP::read_packet(const void* buf, size_t bytes, bool& sync) {
+    const PointerInfo m = QueryPointer(buf);
+    sync |= m.host();
+    if (m.dev) return static_cast<const int32_t*>(m.dev);
+    hip_ok(hipMemcpyAsync(d_stage_, buf, bytes, hipMemcpyDefault, stream_), "hipMemcpyAsync");
+    return d_stage_;
+}
+
 void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info) {
     refuse_half("PreprocessSingle");
     const Tensor& s = job_slice_->slice;
@@ -125,36 +147,26 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
         if (ltu_id >= batch_num_ltus_) {
             const uint64_t k = ltu_id - batch_num_ltus_;
             const uint64_t off = k * P, n = std::min<uint64_t>(P, s.numel - off);
-            const PointerInfo m = QueryPointer(entries_ptr);
-            sync |= m.host();
             // the kernel writes all P words of the block; the reference writes
             // only the n real ones (ppp.cc:102-109), so a partial block is staged
-            int32_t* dst = (m.dev && n == P) ? static_cast<int32_t*>(m.dev) : d_stage_;
-            check(sml_quantize_pack(static_cast<const float*>(s.in_ptr) + off, n, P, config_.general_.num_workers,
-                                    d_recv_exps_ + k, dst, nullptr, round_flags_, stream_),
-                  "sml_quantize_pack");
-            if (dst == d_stage_)
-                hip_ok(hipMemcpyAsync(entries_ptr, d_stage_, n * 4, hipMemcpyDefault, stream_), "hipMemcpyAsync");
-            ltu_id = k + batch_num_ltus_;
+            sync |= write_packet(entries_ptr, d_stage_, n * 4, n == P, [&](int32_t* dst) {
+                check(sml_quantize_pack(static_cast<const float*>(s.in_ptr) + off, n, P, config_.general_.num_workers,
+                                        d_recv_exps_ + k, dst, nullptr, round_flags_, stream_),
+                      "sml_quantize_pack");
+            });
         }
         if (ltu_id < total_main_num_ltus_) {
             const uint64_t off = ltu_id * P, n = std::min<uint64_t>(P, s.numel - off);
-            const PointerInfo m = QueryPointer(extra_info);
-            sync |= m.host();
             // one byte: the int8 exponent in byte 0 of the extra-info slot (byte 1 untouched)
-            int8_t* dst = m.dev ? static_cast<int8_t*>(m.dev) : d_stage_exp_;
-            check(sml_exponents(static_cast<const float*>(s.in_ptr) + off, n, P, dst, stream_), "sml_exponents");
-            if (dst == d_stage_exp_)
-                hip_ok(hipMemcpyAsync(extra_info, d_stage_exp_, 1, hipMemcpyDefault, stream_), "hipMemcpyAsync");
+            sync |= write_packet(extra_info, d_stage_exp_, 1, true, [&](int8_t* dst) {
+                check(sml_exponents(static_cast<const float*>(s.in_ptr) + off, n, P, dst, stream_), "sml_exponents");
+            });
         }
     } else if (s.data_type == INT32) {
         const uint64_t off = ltu_id * P, n = std::min<uint64_t>(P, s.numel - off);
-        const PointerInfo m = QueryPointer(entries_ptr);
-        sync |= m.host();
-        int32_t* dst = m.dev ? static_cast<int32_t*>(m.dev) : d_stage_;
-        check(sml_bswap_i32(static_cast<const int32_t*>(s.in_ptr) + off, dst, n, stream_), "sml_bswap_i32");
-        if (dst == d_stage_)
-            hip_ok(hipMemcpyAsync(entries_ptr, d_stage_, n * 4, hipMemcpyDefault, stream_), "hipMemcpyAsync");
+        sync |= write_packet(entries_ptr, d_stage_, n * 4, true, [&](int32_t* dst) {
+            check(sml_bswap_i32(static_cast<const int32_t*>(s.in_ptr) + off, dst, n, stream_), "sml_bswap_i32");
+        });
     } else {
         throw SwitchMLFatal("unsupported data type");
     }
@@ -175,17 +187,9 @@ void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_
         if (ltu_id >= batch_num_ltus_) {
             const uint64_t k = ltu_id - batch_num_ltus_;
             const uint64_t off = k * P, n = std::min<uint64_t>(P, s.numel - off);
-            const PointerInfo m = QueryPointer(entries_ptr);
-            sync |= m.host();
-            const int32_t* src = static_cast<const int32_t*>(m.dev);
-            if (!src) {
-                hip_ok(hipMemcpyAsync(d_stage_, entries_ptr, n * 4, hipMemcpyDefault, stream_), "hipMemcpyAsync");
-                src = d_stage_;
-            }
-            check(sml_dequantize(src, d_recv_exps_ + k, n, P, config_.general_.num_workers,
-                                 static_cast<float*>(s.out_ptr) + off, 0, stream_),
+            check(sml_dequantize(read_packet(entries_ptr, n * 4, sync), d_recv_exps_ + k, n, P,
+                                 config_.general_.num_workers, static_cast<float*>(s.out_ptr) + off, 0, stream_),
                   "sml_dequantize");
-            ltu_id = k + batch_num_ltus_;
         }
         if (ltu_id < total_main_num_ltus_) {
             // ppp.cc:254-260 stores the scale of the received exponent; the
@@ -196,14 +200,9 @@ void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_
         }
     } else if (s.data_type == INT32) {
         const uint64_t off = ltu_id * P, n = std::min<uint64_t>(P, s.numel - off);
-        const PointerInfo m = QueryPointer(entries_ptr);
-        sync |= m.host();
-        const int32_t* src = static_cast<const int32_t*>(m.dev);
-        if (!src) {
-            hip_ok(hipMemcpyAsync(d_stage_, entries_ptr, n * 4, hipMemcpyDefault, stream_), "hipMemcpyAsync");
-            src = d_stage_;
-        }
-        check(sml_bswap_i32(src, static_cast<int32_t*>(s.out_ptr) + off, n, stream_), "sml_bswap_i32");
+        check(sml_bswap_i32(read_packet(entries_ptr, n * 4, sync), static_cast<int32_t*>(s.out_ptr) + off, n,
+                            stream_),
+              "sml_bswap_i32");
     } else {
         throw SwitchMLFatal("unsupported data type");
     }
@@ -219,10 +218,21 @@ void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_
 void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* ltu_ids, void* const* entries,
                                    void* const* extras) {
     if (n == 0) return;
-    refuse_half(kind == BurstKind::kPre        ? "PreprocessBurst"
-                : kind == BurstKind::kPost     ? "PostprocessBurst"
-                : kind == BurstKind::kExchange ? "PostprocessReuseBurst"
-                                               : "ProcessPostprocessReuseBurst");
+    // a kind's hook, entry point, server op and launch
+    struct Names {
+        const char* hook;
+        const char* entry;
+        uint32_t op;
+        sml_status_t (*launch)(const sml_packet_burst*, void*);
+    };
+    static constexpr Names kNames[] = {   // by BurstKind
+        {"PreprocessBurst", "sml_preprocess_burst", SML_BURST_PRE, sml_preprocess_burst},
+        {"PostprocessBurst", "sml_postprocess_burst", SML_BURST_POST, sml_postprocess_burst},
+        {"PostprocessReuseBurst", "sml_exchange_burst", SML_BURST_EXCHANGE, sml_exchange_burst},
+        {"ProcessPostprocessReuseBurst", "sml_exchange_burst", SML_BURST_EXCHANGE, sml_exchange_burst},
+    };
+    const Names& as = kNames[static_cast<int>(kind)];
+    refuse_half(as.hook);
     const Tensor& s = job_slice_->slice;
     const bool flt = s.data_type == FLOAT32;
     const uint64_t total = total_main_num_ltus_ + (flt ? batch_num_ltus_ : 0);
@@ -272,7 +282,7 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
         dev_of_.emplace(p, a);
         return a;
     };
-    const bool exchange = kind == BurstKind::kExchange || kind == BurstKind::kProcessExchange;
+    const bool exchange = as.op == SML_BURST_EXCHANGE;
     sml_packet_burst b{};
     b.in = static_cast<const float*>(s.in_ptr);
     b.out = static_cast<float*>(s.out_ptr);
@@ -284,8 +294,6 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
     b.batch_num_ltus = flt || exchange ? batch_num_ltus_ : 0;
     b.recv_exps = d_recv_exps_;
     b.flags = (kind == BurstKind::kProcessExchange ? SML_FLAG_PROCESS_PACKET : 0u) | round_flags_;
-    const char* what = kind == BurstKind::kPre ? "sml_preprocess_burst"
-                       : kind == BurstKind::kPost ? "sml_postprocess_burst" : "sml_exchange_burst";
     const bool serve = m.host() && config_.backend_.hip.burst_server;
     if (serve && !server_) {
         check(sml_burst_server_create((uint32_t)ltu_numel_, round_flags_, 100, &server_), "sml_burst_server_create");
@@ -294,8 +302,6 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
         hip_ok(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         server_synced_ = true;
     }
-    const uint32_t op = kind == BurstKind::kPre ? SML_BURST_PRE
-                        : kind == BurstKind::kPost ? SML_BURST_POST : SML_BURST_EXCHANGE;
     for (uint32_t i0 = 0; i0 < n; i0 += SML_MAX_BURST) {
         b.count = std::min<uint32_t>(SML_MAX_BURST, n - i0);
         for (uint32_t i = 0; i < b.count; i++) {
@@ -304,12 +310,10 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
             b.extras[i] = extras ? dev_addr(extras[i0 + i]) : nullptr;
         }
         if (serve) {   // returns with the burst complete
-            check(sml_burst_server_submit(server_, op, &b), "sml_burst_server_submit");
+            check(sml_burst_server_submit(server_, as.op, &b), "sml_burst_server_submit");
             continue;
         }
-        check(kind == BurstKind::kPre ? sml_preprocess_burst(&b, stream_)
-              : kind == BurstKind::kPost ? sml_postprocess_burst(&b, stream_) : sml_exchange_burst(&b, stream_),
-              what);
+        check(as.launch(&b, stream_), as.entry);
     }
     if (serve) return;
     if (m.host() || !stream_ordered_) hip_ok(hipStreamSynchronize(stream_), "hipStreamSynchronize");

@@ -84,6 +84,10 @@ class HipExponentQuantizerPPP : public PrePostProcessor {
     void preprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);
     void postprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);
     void ensure_single_buffers();
+    // the packet buffer of a per-LTU call as a kernel's destination / source
+    template <class T, class Launch>
+    bool write_packet(void* buf, T* stage, size_t bytes, bool in_place, Launch&& launch);
+    const int32_t* read_packet(const void* buf, size_t bytes, bool& sync);
     enum class BurstKind { kPre, kPost, kExchange, kProcessExchange };
     void burst(BurstKind kind, uint32_t n, const uint64_t* ltu_ids, void* const* entries, void* const* extras);
 

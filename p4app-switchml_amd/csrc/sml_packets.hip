@@ -28,6 +28,12 @@
 // bursts (a burst holding both q and q + b is refused), or the exchange
 // burst's, which does both for a received packet in one wave (post of q,
 // then pre of q + b into the same buffer: one launch per rx burst).
+//
+// Each rule is written once.  Device: the phases of one packet (PacketLanes,
+// real_words, load_words / store_words for packets and blocks of the slice,
+// store_block_exponent, pack_block, unpack_block, payload_of), which the three
+// bodies preprocess_one / postprocess_one / exchange_one only compose.  Host:
+// check_burst (every argument rule) and launch_burst (the one launch site).
 #include <algorithm>
 #include <chrono>
 
@@ -35,105 +41,168 @@
 
 namespace sml {
 
-template <int P, bool RNE>
-__device__ __forceinline__ void preprocess_one(const sml_packet_burst& a, uint32_t i) {
-    constexpr int U = P > 256 ? P / 256 : 1;         // 256-element slices per packet
-    constexpr int kLanes = P >= 256 ? kWave : P / 4; // lanes holding a slice
+// ---- the phases of one packet ---------------------------------------------
+// A packet of P words is held by one wave as U slices of 256 words: lane l
+// holds words [j(u), j(u) + 4), j(u) = 256 u + 4 l.  Every phase touches
+// words j + t < n only, and n <= P, so the lanes past a packet of fewer than
+// 256 words (4 l >= P) drop out of every phase without a test of their own.
+template <int P>
+struct PacketLanes {
+    static constexpr int U = P > 256 ? P / 256 : 1;
     const int lane = threadIdx.x & (kWave - 1);
-    const bool act = lane < kLanes;
-    const uint64_t q = a.pkt_ids[i];
-    const uint64_t B = (a.numel + P - 1) / P;
-    if (a.data_type == SML_INT32) {
-        const uint64_t off = q * P, n = a.numel - off < P ? a.numel - off : P;
-        const uint32_t* in = reinterpret_cast<const uint32_t*>(a.in) + off;
-        uint32_t* dst = static_cast<uint32_t*>(a.entries[i]);
+    __device__ __forceinline__ uint64_t j(int u) const { return (uint64_t)u * 256 + lane * 4; }
+};
+
+// The real words of block k: P, or what the slice has left in its last block.
+template <int P>
+__device__ __forceinline__ uint64_t real_words(const sml_packet_burst& a, uint64_t k) {
+    return a.numel - k * P < P ? a.numel - k * P : P;
+}
+
+// A lane's four words [j, j + 4) of the n words of a buffer: one 16-byte access
+// where the group is whole (a packet over PCIe then costs one access per 64 B
+// line, not four), single words in the group that n cuts.  The load gives 0
+// past n; the store writes nothing at or past n.
+__device__ __forceinline__ void load_group(const uint32_t* buf, uint64_t j, uint64_t n, uint32_t (&v)[4]) {
+    if (j + 4 <= n) {
+        const u4a q = *reinterpret_cast<const u4a*>(buf + j);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
 #pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const uint64_t j = (uint64_t)u * 256 + lane * 4 + t;
-                if (act && j < n) dst[j] = bswap(in[j]);
-            }
-        return;
-    }
-    if (q >= a.batch_num_ltus) {
-        const uint64_t k = q - a.batch_num_ltus;
-        const uint64_t off = k * P, n = a.numel - off < P ? a.numel - off : P;
-        const uint64_t body = n / 16 * 16;          // VCL=1: RNE on the 16-aligned body of the block
-        const float s = scale_for(a.num_workers, (int)a.recv_exps[k]);
-        const float* in = a.in + off;
-        uint32_t* dst = static_cast<uint32_t*>(a.entries[i]);
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t j = (uint64_t)u * 256 + lane * 4;
-            const f4 x = act ? load4_guarded(in + j, j, n) : mkf4(0, 0, 0, 0);
-            const u4 w = quantize4<RNE>(x, s, j, body);
-            if (act && j + 4 <= n) {
-                *reinterpret_cast<u4a*>(dst + j) = u4a{bswap(w.x), bswap(w.y), bswap(w.z), bswap(w.w)};
-            } else {
-                if (act && j + 0 < n) dst[j + 0] = bswap(w.x);
-                if (act && j + 1 < n) dst[j + 1] = bswap(w.y);
-                if (act && j + 2 < n) dst[j + 2] = bswap(w.z);
-                if (act && j + 3 < n) dst[j + 3] = bswap(w.w);
-            }
-        }
-    }
-    if (q < B) {
-        const uint64_t off = q * P, n = a.numel - off < P ? a.numel - off : P;
-        const float* in = a.in + off;
-        uint32_t m = 0;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t j = (uint64_t)u * 256 + lane * 4;
-            if (act) m = umax(m, max4(load4_guarded(in + j, j, n)));
-        }
-        m = group_max<256>(m);                     // the wave's max = the packet's (idle lanes hold 0)
-        if (lane == 0) *static_cast<int8_t*>(a.extras[i]) = (int8_t)exponent_of(m);
+        for (int t = 0; t < 4; t++) v[t] = j + t < n ? buf[j + t] : 0u;
     }
 }
 
+__device__ __forceinline__ void store_group(uint32_t* buf, uint64_t j, uint64_t n, const uint32_t (&v)[4]) {
+    if (j + 4 <= n) {
+        *reinterpret_cast<u4a*>(buf + j) = u4a{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            if (j + t < n) buf[j + t] = v[t];
+    }
+}
+
+// Words [0, n) of a packet buffer <-> w.
+template <int P, int U>
+__device__ __forceinline__ void load_words(PacketLanes<P> g, const uint32_t* buf, uint64_t n, uint32_t (&w)[U][4]) {
+#pragma unroll
+    for (int u = 0; u < U; u++) load_group(buf, g.j(u), n, w[u]);
+}
+
+template <int P, int U>
+__device__ __forceinline__ void store_words(PacketLanes<P> g, uint32_t* buf, uint64_t n, const uint32_t (&w)[U][4]) {
+#pragma unroll
+    for (int u = 0; u < U; u++) store_group(buf, g.j(u), n, w[u]);
+}
+
+// Block k of the slice as words (FLOAT32: its bits), for load_words.
 template <int P>
-__device__ __forceinline__ void postprocess_one(const sml_packet_burst& a, uint32_t i) {
-    constexpr int U = P > 256 ? P / 256 : 1;
-    constexpr int kLanes = P >= 256 ? kWave : P / 4;
-    const int lane = threadIdx.x & (kWave - 1);
-    const bool act = lane < kLanes;
+__device__ __forceinline__ const uint32_t* block_words(const sml_packet_burst& a, uint64_t k) {
+    return reinterpret_cast<const uint32_t*>(a.in) + k * P;
+}
+__device__ __forceinline__ f4 as_f4(const uint32_t (&v)[4]) {
+    return mkf4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+}
+
+// The exponent of the block in x (0 past its real words) into byte 0 of the
+// packet's extra-info slot; byte 1 is never written (ppp.cc:154).
+template <int P, int U>
+__device__ __forceinline__ void store_block_exponent(PacketLanes<P> g, const uint32_t (&x)[U][4], void* extra) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int u = 0; u < U; u++) m = umax(m, max4(as_f4(x[u])));
+    m = group_max<256>(m);                                  // the wave's max = the packet's
+    if (g.lane == 0) *static_cast<int8_t*>(extra) = (int8_t)exponent_of(m);
+}
+
+// The n words of the block in x, big-endian, into w; the other words of w
+// keep their value.  FLOAT32: quantized with scale s, VCL=1 rounding (RNE) on
+// the 16-aligned body of the block; INT32: as they are.
+template <int P, bool RNE, int U>
+__device__ __forceinline__ void pack_block(PacketLanes<P> g, bool flt, const uint32_t (&x)[U][4], float s, uint64_t n,
+                                           uint32_t (&w)[U][4]) {
+    const uint64_t body = n / 16 * 16;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint64_t j = g.j(u);
+        const u4 v = flt ? quantize4<RNE>(as_f4(x[u]), s, j, body) : mku4(x[u][0], x[u][1], x[u][2], x[u][3]);
+        const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            if (j + t < n) w[u][t] = bswap(vv[t]);
+    }
+}
+
+// Words [0, n) of w into the n words of a block of the output: dequantized
+// with scale s (FLOAT32), or byte-swapped (INT32).
+template <int P, int U>
+__device__ __forceinline__ void unpack_block(PacketLanes<P> g, bool flt, const uint32_t (&w)[U][4], float s, uint64_t n,
+                                             uint32_t* out) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        uint32_t v[4];   // every word of the group converted, whole group or not: four divisions in flight
+#pragma unroll
+        for (int t = 0; t < 4; t++) v[t] = flt ? __float_as_uint(dequantize1(bswap(w[u][t]), s)) : bswap(w[u][t]);
+        store_group(out, g.j(u), n, v);
+    }
+}
+
+// Which block packet q carries: FLOAT32 packets run one window behind their
+// exponents (block q - b, none for q < b); INT32 packet q carries block q.
+struct Payload { bool on; uint64_t k; };
+__device__ __forceinline__ Payload payload_of(const sml_packet_burst& a, bool flt, uint64_t q) {
+    const bool on = !flt || q >= a.batch_num_ltus;
+    return {on, !on ? 0 : flt ? q - a.batch_num_ltus : q};
+}
+
+// ---- the three per-packet bodies ------------------------------------------
+// PreprocessSingle of packet q: its block into the packet with the scale of
+// the exponent received for that block (recv_exps, in memory), only the real
+// words written; the exponent of block q into the extra slot (FLOAT32, q < B).
+template <int P, bool RNE>
+__device__ __forceinline__ void preprocess_one(const sml_packet_burst& a, uint32_t i) {
+    const PacketLanes<P> g{};
+    constexpr int U = PacketLanes<P>::U;
     const uint64_t q = a.pkt_ids[i];
     const uint64_t B = (a.numel + P - 1) / P;
-    const uint32_t* src = static_cast<const uint32_t*>(a.entries[i]);
-    if (a.data_type == SML_INT32) {
-        const uint64_t off = q * P, n = a.numel - off < P ? a.numel - off : P;
-        uint32_t* out = reinterpret_cast<uint32_t*>(a.out) + off;
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const uint64_t j = (uint64_t)u * 256 + lane * 4 + t;
-                if (act && j < n) out[j] = bswap(src[j]);
-            }
-        return;
+    const bool flt = a.data_type == SML_FLOAT32;
+    const Payload pay = payload_of(a, flt, q);
+    uint32_t x[U][4];
+    if (pay.on) {
+        const uint64_t n = real_words<P>(a, pay.k);
+        const int e = flt ? (int)a.recv_exps[pay.k] : 0;   // asked for ahead of the block: one wait for both
+        uint32_t w[U][4] = {};
+        load_words(g, block_words<P>(a, pay.k), n, x);
+        const float s = flt ? scale_for(a.num_workers, e) : 0.0f;
+        pack_block<P, RNE>(g, flt, x, s, n, w);
+        store_words(g, static_cast<uint32_t*>(a.entries[i]), n, w);
     }
-    if (q >= a.batch_num_ltus) {
-        const uint64_t k = q - a.batch_num_ltus;
-        const uint64_t off = k * P, n = a.numel - off < P ? a.numel - off : P;
-        const float s = scale_for(a.num_workers, (int)a.recv_exps[k]);
-        float* out = a.out + off;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t j = (uint64_t)u * 256 + lane * 4;
-            if (act && j + 4 <= n) {   // one 16-B read of the packet per lane
-                const u4a v = *reinterpret_cast<const u4a*>(src + j);
-                const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int t = 0; t < 4; t++) out[j + t] = dequantize1(bswap(vv[t]), s);
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-                    if (act && j + t < n) out[j + t] = dequantize1(bswap(src[j + t]), s);
-            }
-        }
+    if (flt && q < B) {
+        load_words(g, block_words<P>(a, q), real_words<P>(a, q), x);
+        store_block_exponent(g, x, a.extras[i]);
     }
-    if (q < B && lane == 0) a.recv_exps[q] = *static_cast<const int8_t*>(a.extras[i]);
+}
+
+// PostprocessSingle of packet q: its block out of the packet into the slice
+// output; the packet's exponent byte kept as block q's received exponent.
+template <int P>
+__device__ __forceinline__ void postprocess_one(const sml_packet_burst& a, uint32_t i) {
+    const PacketLanes<P> g{};
+    constexpr int U = PacketLanes<P>::U;
+    const uint64_t q = a.pkt_ids[i];
+    const uint64_t B = (a.numel + P - 1) / P;
+    const bool flt = a.data_type == SML_FLOAT32;
+    const Payload pay = payload_of(a, flt, q);
+    if (pay.on) {
+        const uint64_t n = real_words<P>(a, pay.k);
+        const int e = flt ? (int)a.recv_exps[pay.k] : 0;   // asked for ahead of the packet: one wait for both
+        uint32_t w[U][4];
+        load_words(g, static_cast<const uint32_t*>(a.entries[i]), n, w);
+        const float s = flt ? scale_for(a.num_workers, e) : 0.0f;
+        unpack_block(g, flt, w, s, n, reinterpret_cast<uint32_t*>(a.out) + pay.k * P);
+    }
+    if (flt && q < B && g.lane == 0) a.recv_exps[q] = *static_cast<const int8_t*>(a.extras[i]);
 }
 
 // One wave per RECEIVED packet q, the DPDK receive loop's two calls on one
@@ -154,54 +223,30 @@ __device__ __forceinline__ void postprocess_one(const sml_packet_burst& a, uint3
 // posted write may overtake an outstanding read.
 template <int P, bool RNE, bool PROC>
 __device__ __forceinline__ void exchange_one(const sml_packet_burst& a, uint32_t i) {
-    constexpr int U = P > 256 ? P / 256 : 1;
-    constexpr int kLanes = P >= 256 ? kWave : P / 4;
-    const int lane = threadIdx.x & (kWave - 1);
-    const bool act = lane < kLanes;
+    const PacketLanes<P> g{};
+    constexpr int U = PacketLanes<P>::U;
     const uint64_t q = a.pkt_ids[i];
     const uint64_t B = (a.numel + P - 1) / P;
     const uint64_t b = a.batch_num_ltus;
     const bool flt = a.data_type == SML_FLOAT32;
-    auto real = [&](uint64_t k) -> uint64_t { return a.numel - k * P < P ? a.numel - k * P : P; };
     uint32_t* ent = static_cast<uint32_t*>(a.entries[i]);
-    const int8_t* ext = static_cast<const int8_t*>(a.extras[i]);
 
     // what each half touches: post reads words [0, n_post) of the packet
-    // (all P under PROC), pre rewrites words [0, n_pre)
-    const bool post_pay = flt ? q >= b : true;
-    const uint64_t n_post = !post_pay ? 0 : real(flt ? q - b : q);
-    const bool pre = flt ? q < B : q + b < B;
-    const uint64_t n_pre = !pre ? 0 : real(flt ? q : q + b);
-    const bool pre_exp = flt && q + b < B;
-    const uint64_t n_read = PROC ? P : n_post;
+    // (all P under PROC), pre rewrites words [0, n_pre) with block k_pre
+    const Payload post = payload_of(a, flt, q);
+    const uint64_t n_post = post.on ? real_words<P>(a, post.k) : 0;
+    const uint64_t k_pre = flt ? q : q + b;
+    const uint64_t n_pre = k_pre < B ? real_words<P>(a, k_pre) : 0;
+    const uint64_t n_exp = flt && q + b < B ? real_words<P>(a, q + b) : 0;   // the block whose exponent goes out
 
-    // ---- every load up front
-    uint32_t w[U][4];
-    f4 xq[U], xe[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        {   // one 16-B access per lane where the group is whole (a packet over
-            // PCIe then costs one read per 64 B line, not four)
-            const uint64_t j = (uint64_t)u * 256 + lane * 4;
-            if (act && j + 4 <= n_read) {
-                const u4a v = *reinterpret_cast<const u4a*>(ent + j);
-                w[u][0] = v.x, w[u][1] = v.y, w[u][2] = v.z, w[u][3] = v.w;
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; t++) w[u][t] = act && j + t < n_read ? ent[j + t] : 0u;
-            }
-        }
-        const uint64_t j = (uint64_t)u * 256 + lane * 4;
-        if (flt) {
-            xq[u] = act && pre ? load4_guarded(a.in + q * P + j, j, n_pre) : mkf4(0, 0, 0, 0);
-            xe[u] = act && pre_exp ? load4_guarded(a.in + (q + b) * P + j, j, real(q + b)) : mkf4(0, 0, 0, 0);
-        } else {
-            const float* src = a.in + (q + b) * P + j;   // int32 words, read as raw bits
-            xq[u] = act && pre ? load4_guarded(src, j, n_pre) : mkf4(0, 0, 0, 0);
-        }
-    }
-    const int e_recv = flt && q < B ? (int)*ext : 0;     // the packet's (aggregated) exponent byte
-    const int e_post = flt && q >= b ? (int)a.recv_exps[q - b] : 0;
+    // ---- every load up front; the packet's own (words, aggregated exponent
+    // byte: they may cross PCIe) first, so that they are in flight together
+    uint32_t w[U][4], xq[U][4], xe[U][4];
+    load_words(g, ent, PROC ? P : n_post, w);
+    const int e_recv = flt && q < B ? (int)*static_cast<const int8_t*>(a.extras[i]) : 0;
+    const int e_post = flt && post.on ? (int)a.recv_exps[post.k] : 0;
+    load_words(g, block_words<P>(a, n_pre ? k_pre : 0), n_pre, xq);
+    load_words(g, block_words<P>(a, n_exp ? q + b : 0), n_exp, xe);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
     // ---- ProcessPacket, postprocess
@@ -212,61 +257,14 @@ __device__ __forceinline__ void exchange_one(const sml_packet_burst& a, uint32_t
 #pragma unroll
             for (int t = 0; t < 4; t++) w[u][t] = bswap(bswap(w[u][t]) * W);
     }
-    if (post_pay) {
-        const uint64_t k = flt ? q - b : q;
-        const float s = flt ? scale_for(W, e_post) : 0.0f;
-        uint32_t* out = reinterpret_cast<uint32_t*>(a.out) + k * P;
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const uint64_t j = (uint64_t)u * 256 + lane * 4 + t;
-                if (act && j < n_post)
-                    out[j] = flt ? __float_as_uint(dequantize1(bswap(w[u][t]), s)) : bswap(w[u][t]);
-            }
-    }
-    if (flt && q < B && lane == 0) a.recv_exps[q] = (int8_t)e_recv;
+    unpack_block(g, flt, w, flt ? scale_for(W, e_post) : 0.0f, n_post, reinterpret_cast<uint32_t*>(a.out) + post.k * P);
+    if (flt && q < B && g.lane == 0) a.recv_exps[q] = (int8_t)e_recv;
 
-    // ---- preprocess of q + b into the same buffer
-    if (pre) {
-        const float s = flt ? scale_for(W, e_recv) : 0.0f;
-        const uint64_t body = n_pre / 16 * 16;              // VCL=1: RNE on the 16-aligned body
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t j = (uint64_t)u * 256 + lane * 4;
-            u4 v;
-            if (flt) {
-                v = quantize4<RNE>(xq[u], s, j, body);
-            } else {
-                v = mku4(__float_as_uint(xq[u].x), __float_as_uint(xq[u].y), __float_as_uint(xq[u].z),
-                         __float_as_uint(xq[u].w));
-            }
-            const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-                if (act && j + t < n_pre) w[u][t] = bswap(vv[t]);
-        }
-    }
-    // the buffer's words: the new packet's, or (PROC) the processed ones
-    const uint64_t n_write = PROC ? P : n_pre;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const uint64_t j = (uint64_t)u * 256 + lane * 4;
-        if (act && j + 4 <= n_write) {
-            *reinterpret_cast<u4a*>(ent + j) = u4a{w[u][0], w[u][1], w[u][2], w[u][3]};
-        } else {
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-                if (act && j + t < n_write) ent[j + t] = w[u][t];
-        }
-    }
-    if (pre_exp) {
-        uint32_t m = 0;
-#pragma unroll
-        for (int u = 0; u < U; u++) m = umax(m, max4(xe[u]));
-        m = group_max<256>(m);                              // idle lanes hold 0
-        if (lane == 0) *static_cast<int8_t*>(a.extras[i]) = (int8_t)exponent_of(m);
-    }
+    // ---- preprocess of q + b into the same buffer: its words are the new
+    // packet's, or (PROC) the processed ones where the new packet has none
+    pack_block<P, RNE>(g, flt, xq, flt ? scale_for(W, e_recv) : 0.0f, n_pre, w);
+    store_words(g, ent, PROC ? P : n_pre, w);
+    if (n_exp) store_block_exponent(g, xe, a.extras[i]);
 }
 
 // One launch per burst: a wave per packet.
@@ -391,15 +389,18 @@ __global__ __launch_bounds__(kServerThreads) void k_burst_server(ServerCtl* ctl,
     if (tid == 0) __hip_atomic_store(&ctl->exited[blockIdx.x], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Host checks shared by the entry points.  `window`: the exchange burst's
-// packet window b applies to INT32 slices too (the next packet is q + b).
-static sml_status_t check_burst(const sml_packet_burst* a, bool window = false) {
+// Host checks of a burst for op SML_BURST_PRE / POST / EXCHANGE, shared by the
+// launched entry points and the server.  The preprocess reads the slice, the
+// postprocess writes the output, the exchange does both; its packet window b
+// applies to INT32 slices too (the next packet is q + b).
+static sml_status_t check_burst(const sml_packet_burst* a, uint32_t op) {
+    const bool window = op == SML_BURST_EXCHANGE;
     if (!a) return SML_ERR_INVALID_ARG;
     if (!valid_packet(a->packet_numel)) return SML_ERR_UNSUPPORTED;
     if (a->count > SML_MAX_BURST || a->num_workers == 0) return SML_ERR_INVALID_ARG;
     if (a->data_type != SML_FLOAT32 && a->data_type != SML_INT32) return SML_ERR_UNSUPPORTED;
     if (a->count == 0) return SML_OK;
-    if (!a->in && !a->out) return SML_ERR_INVALID_ARG;
+    if ((op != SML_BURST_POST && !a->in) || (op != SML_BURST_PRE && !a->out)) return SML_ERR_INVALID_ARG;
     const uint64_t P = a->packet_numel;
     const uint64_t B = sml_num_blocks(a->numel, (uint32_t)P);
     const bool flt = a->data_type == SML_FLOAT32;
@@ -428,41 +429,11 @@ static sml_status_t check_burst(const sml_packet_burst* a, bool window = false) 
     return SML_OK;
 }
 
-}  // namespace sml
-
-using namespace sml;
-
-extern "C" {
-
-sml_status_t sml_preprocess_burst(const sml_packet_burst* burst, void* stream) {
-    sml_status_t st = check_burst(burst);
+// One launch for the burst, a wave per packet, on `stream`: the kernel of op
+// for the burst's packet size and the flags that op knows.
+static sml_status_t launch_burst(const sml_packet_burst* burst, uint32_t op, void* stream) {
+    const sml_status_t st = check_burst(burst, op);
     if (st != SML_OK || burst->count == 0) return st;
-    if (!burst->in) return SML_ERR_INVALID_ARG;
-    const sml_packet_burst& a = *burst;
-    const dim3 grid((a.count + kWavesPerBlock - 1) / kWavesPerBlock);
-    const hipStream_t s = (hipStream_t)stream;
-    const bool rne = (a.flags & SML_FLAG_ROUND_RNE) != 0;
-    dispatch_packet(a.packet_numel, [&](auto Pc) {
-        dispatch_bools([&](auto RNE) { k_preprocess_burst<Pc(), RNE()><<<grid, kBlockThreads, 0, s>>>(a); }, rne);
-    });
-    return launch_check();
-}
-
-sml_status_t sml_postprocess_burst(const sml_packet_burst* burst, void* stream) {
-    sml_status_t st = check_burst(burst);
-    if (st != SML_OK || burst->count == 0) return st;
-    if (!burst->out) return SML_ERR_INVALID_ARG;
-    const sml_packet_burst& a = *burst;
-    const dim3 grid((a.count + kWavesPerBlock - 1) / kWavesPerBlock);
-    const hipStream_t s = (hipStream_t)stream;
-    dispatch_packet(a.packet_numel, [&](auto Pc) { k_postprocess_burst<Pc()><<<grid, kBlockThreads, 0, s>>>(a); });
-    return launch_check();
-}
-
-sml_status_t sml_exchange_burst(const sml_packet_burst* burst, void* stream) {
-    sml_status_t st = check_burst(burst, true);
-    if (st != SML_OK || burst->count == 0) return st;
-    if (!burst->in || !burst->out) return SML_ERR_INVALID_ARG;
     const sml_packet_burst& a = *burst;
     const dim3 grid((a.count + kWavesPerBlock - 1) / kWavesPerBlock);
     const hipStream_t s = (hipStream_t)stream;
@@ -470,10 +441,30 @@ sml_status_t sml_exchange_burst(const sml_packet_burst* burst, void* stream) {
     const bool proc = (a.flags & SML_FLAG_PROCESS_PACKET) != 0;
     dispatch_packet(a.packet_numel, [&](auto Pc) {
         dispatch_bools([&](auto RNE, auto PROC) {
-            k_exchange_burst<Pc(), RNE(), PROC()><<<grid, kBlockThreads, 0, s>>>(a);
+            if (op == SML_BURST_PRE) k_preprocess_burst<Pc(), RNE()><<<grid, kBlockThreads, 0, s>>>(a);
+            else if (op == SML_BURST_POST) k_postprocess_burst<Pc()><<<grid, kBlockThreads, 0, s>>>(a);
+            else k_exchange_burst<Pc(), RNE(), PROC()><<<grid, kBlockThreads, 0, s>>>(a);
         }, rne, proc);
     });
     return launch_check();
+}
+
+}  // namespace sml
+
+using namespace sml;
+
+extern "C" {
+
+sml_status_t sml_preprocess_burst(const sml_packet_burst* burst, void* stream) {
+    return launch_burst(burst, SML_BURST_PRE, stream);
+}
+
+sml_status_t sml_postprocess_burst(const sml_packet_burst* burst, void* stream) {
+    return launch_burst(burst, SML_BURST_POST, stream);
+}
+
+sml_status_t sml_exchange_burst(const sml_packet_burst* burst, void* stream) {
+    return launch_burst(burst, SML_BURST_EXCHANGE, stream);
 }
 
 }  // extern "C"
@@ -579,9 +570,8 @@ sml_status_t sml_burst_server_create(uint32_t packet_numel, uint32_t flags, uint
 
 sml_status_t sml_burst_server_submit(sml_burst_server* s, uint32_t op, const sml_packet_burst* burst) {
     if (!s || op > SML_BURST_EXCHANGE) return SML_ERR_INVALID_ARG;
-    sml_status_t st = sml::check_burst(burst, op == SML_BURST_EXCHANGE);
+    sml_status_t st = sml::check_burst(burst, op);
     if (st != SML_OK || burst->count == 0) return st;
-    if ((op != SML_BURST_POST && !burst->in) || (op != SML_BURST_PRE && !burst->out)) return SML_ERR_INVALID_ARG;
     if (burst->packet_numel != s->packet_numel || ((burst->flags & SML_FLAG_ROUND_RNE) != 0) != s->rne)
         return SML_ERR_INVALID_ARG;   // fixed per server
     // not running, left its loop, or close to its idle exit: (re)start it, so

@@ -128,24 +128,22 @@ def test_argument_validation_without_gpu(sw):
     assert L.sml_quantize_pack(None, 0, 100, 1, None, None, None, 0, None) == sw.SML_ERR_UNSUPPORTED
 
 
-def test_burst_validation_without_gpu(sw):
-    """sml_{pre,post}process_burst / sml_exchange_burst refuse a malformed
-    burst before any HIP call: too many packets, an id past B (+ b), a
-    duplicate id, q and q + b together, a zero window for the exchange, a
-    missing extra slot for a FLOAT32 packet that carries an exponent."""
-    L = sw.lib()
+def burst_maker(sw):
+    """burst(ids, ...): a reference to a FLOAT32 sml_packet_burst over host
+    buffers (B = 16 blocks of 256), for the checks that return before any HIP
+    call.  The buffers live as long as the returned function."""
     x = (ctypes.c_float * 4096)()
     o = (ctypes.c_float * 4096)()
     recv = (ctypes.c_int8 * 16)()
     ring = (ctypes.c_int32 * 256)()
     extra = (ctypes.c_uint8 * 2)()
 
-    def burst(ids, b=4, with_extra=True, count=None):
+    def burst(ids, b=4, with_extra=True, count=None, null=(), packet_numel=256):
         bt = sw.PacketBurst()
-        bt.in_ = ctypes.addressof(x)
-        bt.out = ctypes.addressof(o)
+        bt.in_ = None if "in" in null else ctypes.addressof(x)
+        bt.out = None if "out" in null else ctypes.addressof(o)
         bt.numel = 4096
-        bt.packet_numel = 256                  # B = 16
+        bt.packet_numel = packet_numel         # 256: B = 16
         bt.num_workers = 1
         bt.data_type = 0
         bt.batch_num_ltus = b
@@ -157,6 +155,17 @@ def test_burst_validation_without_gpu(sw):
             bt.extras[i] = ctypes.addressof(extra) if with_extra else None
         return ctypes.byref(bt)
 
+    return burst
+
+
+def test_burst_validation_without_gpu(sw):
+    """sml_{pre,post}process_burst / sml_exchange_burst refuse a malformed
+    burst before any HIP call: too many packets, an id past B (+ b), a
+    duplicate id, q and q + b together, a zero window for the exchange, a
+    missing extra slot for a FLOAT32 packet that carries an exponent."""
+    L = sw.lib()
+    burst = burst_maker(sw)
+
     bad = sw.SML_ERR_INVALID_ARG
     for fn in (L.sml_preprocess_burst, L.sml_postprocess_burst, L.sml_exchange_burst):
         assert fn(burst([0], count=65), None) == bad           # > SML_MAX_BURST
@@ -167,6 +176,20 @@ def test_burst_validation_without_gpu(sw):
         assert fn(burst([]), None) == sw.SML_OK                # nothing to do
     assert L.sml_exchange_burst(burst([1], b=0), None) == bad  # the exchange needs its window
     assert L.sml_exchange_burst(burst([1], b=17), None) == bad  # b > B
+
+
+def test_burst_null_slice_pointer_status_order(sw):
+    """Pre needs `in`, post needs `out`, the exchange needs both: a burst with
+    packets and the forbidden NULL is an invalid argument, the same burst
+    without packets is nothing to do, and with a bad packet size as well the
+    earlier check (unsupported) decides."""
+    L = sw.lib()
+    burst = burst_maker(sw)
+    for fn, null in ((L.sml_preprocess_burst, "in"), (L.sml_postprocess_burst, "out"),
+                     (L.sml_exchange_burst, "in"), (L.sml_exchange_burst, "out")):
+        assert fn(burst([1], null=(null,)), None) == sw.SML_ERR_INVALID_ARG
+        assert fn(burst([], null=(null,)), None) == sw.SML_OK
+        assert fn(burst([1], null=(null,), packet_numel=100), None) == sw.SML_ERR_UNSUPPORTED
 
 
 def test_burst_server_validation_without_gpu(sw):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from switchml_amd import PACKET_NUMELS
 
 
 def sw():
@@ -25,9 +26,12 @@ def sw():
     return s
 
 
-def run_bursts(x, P, W, b_max, ring_place, cuda, rng, burst_cap=64):
+def run_bursts(x, P, W, b_max, ring_place, cuda, rng, burst_cap=64, srv=None, more=None):
     """The dummy packet loop, burst by burst, through the C-ABI; returns
-    (captured packet exps, captured packet payloads, output, b)."""
+    (captured packet exps, captured packet payloads, output, b).  `srv`: every
+    burst goes through that BurstServer (BURST_PRE / BURST_POST) instead of a
+    launch.  `more`: a dict that receives every packet's whole slot as sent
+    (stale tail included) and the received exponents."""
     import torch
     s = sw()
     n = x.size
@@ -47,6 +51,7 @@ def run_bursts(x, P, W, b_max, ring_place, cuda, rng, burst_cap=64):
     rbase, ebase = ring.data_ptr(), extra.data_ptr()
     cap_e = np.zeros(total, dtype=np.int8)
     cap_p = np.zeros((total, P), dtype=np.uint32)
+    cap_slot = np.zeros((total, P), dtype=np.uint32)
     stream = torch.cuda.current_stream(cuda)
 
     def bursts(ids, pre):
@@ -57,7 +62,10 @@ def run_bursts(x, P, W, b_max, ring_place, cuda, rng, burst_cap=64):
             slots = [q % b for q in part]
             bt = s.packet_burst(xd, out, P, W, b, recv, part, [rbase + sl * P * 4 for sl in slots],
                                 [ebase + sl * 2 for sl in slots])
-            (s.preprocess_burst if pre else s.postprocess_burst)(bt, stream)
+            if srv is not None:
+                srv.submit(s.BURST_PRE if pre else s.BURST_POST, bt)
+            else:
+                (s.preprocess_burst if pre else s.postprocess_burst)(bt, stream)
         torch.cuda.synchronize()
 
     def snapshot():
@@ -69,6 +77,7 @@ def run_bursts(x, P, W, b_max, ring_place, cuda, rng, burst_cap=64):
         for q in ids:
             sl = q % b
             cap_e[q] = eh[sl * 2].astype(np.int8) if q < B else 0
+            cap_slot[q] = rh[sl]
             if q >= b:
                 m = min(P, n - (q - b) * P)
                 cap_p[q, :m] = rh[sl, :m]
@@ -91,6 +100,8 @@ def run_bursts(x, P, W, b_max, ring_place, cuda, rng, burst_cap=64):
         prev = snapshot()
         bursts(nxt, True)
         capture(nxt, prev)
+    if more is not None:
+        more.update(slots=cap_slot, recv=recv.cpu().numpy())
     return cap_e, cap_p, out.cpu().numpy(), b
 
 
@@ -549,3 +560,194 @@ def test_burst_server_never_replays_an_unanswered_doorbell(cuda):
     srv.close()
     ref = O.dummy_packet_stream(x, P=P, batch_max=b, num_workers=W)[2]
     assert np.array_equal(out.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+
+
+SLOT_FILL = 0x5A5A5A5A       # a packet slot's words before any packet was built
+OUT_FILL = 0x0DD0BEEF        # the output's words before any packet was post-processed
+
+
+def partial_last_block(P):
+    """n with B = 4 blocks, the last one of P/2 + 3 real words (n % 4 == 3)."""
+    return 3 * P + P // 2 + 3
+
+
+class Int32Ring:
+    """An INT32 slice, a ring of b = 2 packet slots in device memory and the
+    output, driven through the launched entry points or a BurstServer, next to
+    a numpy model of the same calls: the INT32 pre/post-processor is a byte
+    swap of the block's real words (ppp.cc:158-190, 262-298), ProcessPacket a
+    multiplication of all P host-order words by W (dummy_backend.cc:72-84)."""
+    b = 2
+
+    def __init__(self, P, cuda, srv, seed):
+        import torch
+        self.s, self.P, self.srv, self.n = sw(), P, srv, partial_last_block(P)
+        self.B = O.num_blocks(self.n, P)
+        assert self.B == 4 and self.n % 4 == 3
+        self.x = np.random.default_rng(seed).integers(-2 ** 31, 2 ** 31, self.n, dtype=np.int64).astype(np.int32)
+        self.xd = torch.from_numpy(self.x).to(cuda)
+        self.ring = torch.full((self.b * P,), SLOT_FILL, dtype=torch.int32, device=cuda)
+        self.out = torch.full((self.n,), OUT_FILL, dtype=torch.int32, device=cuda)
+        self.stream = torch.cuda.current_stream(cuda)
+        self.want_slots = np.full((self.b, P), SLOT_FILL, dtype=np.uint32)
+        self.want_out = np.full(self.n, OUT_FILL, dtype=np.uint32)
+
+    def real(self, q):
+        return min(self.P, self.n - q * self.P)
+
+    def block(self, q):
+        return self.x[q * self.P:q * self.P + self.real(q)].view(np.uint32)
+
+    def slots(self):
+        import torch
+        torch.cuda.synchronize()
+        return self.ring.cpu().numpy().view(np.uint32).reshape(self.b, self.P).copy()
+
+    def call(self, op, ids, W=1, flags=0):
+        s, P, b = self.s, self.P, self.b
+        before = self.slots()
+        assert np.array_equal(before, self.want_slots)
+        bt = s.packet_burst(self.xd, self.out, P, W, b, None, ids,
+                            [self.ring.data_ptr() + (q % b) * P * 4 for q in ids], [0] * len(ids), flags=flags)
+        if self.srv is not None:
+            self.srv.submit(op, bt)
+        else:
+            {s.BURST_PRE: s.preprocess_burst, s.BURST_POST: s.postprocess_burst,
+             s.BURST_EXCHANGE: s.exchange_burst}[op](bt, self.stream)
+        proc = bool(flags & s.FLAG_PROCESS_PACKET)
+        for q in ids:                                   # the model
+            w = self.want_slots[q % b]                  # a view: edits land in the model
+            if op == s.BURST_PRE:
+                w[:self.real(q)] = O.bswap32(self.block(q))
+                continue
+            if proc:                                    # ProcessPacket: all P words
+                w[:] = O.bswap32((O.bswap32(w).astype(np.uint64) * W % (1 << 32)).astype(np.uint32))
+            m = self.real(q)
+            self.want_out[q * P:q * P + m] = O.bswap32(w[:m])
+            if op == s.BURST_EXCHANGE and q + b < self.B:
+                w[:self.real(q + b)] = O.bswap32(self.block(q + b))
+        after = self.slots()
+        got_out = self.out.cpu().numpy().view(np.uint32)
+        for q in ids:
+            sl = q % b
+            nxt = q if op == s.BURST_PRE else q + b if op == s.BURST_EXCHANGE and q + b < self.B else None
+            m = self.real(nxt) if nxt is not None else 0
+            if nxt is not None:
+                assert np.array_equal(after[sl, :m], O.bswap32(self.block(nxt))), f"real words of packet {nxt}"
+            if not proc:
+                assert np.array_equal(after[sl, m:], before[sl, m:]), f"slot {sl}: words past {m} overwritten"
+            else:
+                done = O.bswap32((O.bswap32(before[sl]).astype(np.uint64) * W % (1 << 32)).astype(np.uint32))
+                assert np.array_equal(after[sl, m:], done[m:]), f"slot {sl}: words past {m} not the processed ones"
+        assert np.array_equal(after, self.want_slots)
+        assert np.array_equal(got_out, self.want_out)
+        return after
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["launch", "server"])
+@pytest.mark.parametrize("P", PACKET_NUMELS)
+def test_int32_bursts_every_packet_size(cuda, P, route):
+    """INT32 slices for every packet size, with a partial last block whose
+    length is no multiple of 4, through the launched entry points and through
+    the burst server.  Pre / post bursts: after every call the slots hold the
+    byte-swapped real words, every word past a partial block's real words is
+    exactly what the slot held before the call, and at the end out == x.  The
+    same slice through the exchange, without and with FLAG_PROCESS_PACKET
+    (W = 3): with the flag out is x * 3 (mod 2^32), a slot's words past the
+    new packet's real words are the processed ones, and the slots of packets
+    2 and 3 — no successor — hold all P processed words; without it those
+    words are untouched."""
+    s = sw()
+    srv = s.BurstServer(P) if route == "server" else None
+    try:
+        r = Int32Ring(P, cuda, srv, seed=P)
+        for ids in ([0, 1], [2, 3]):
+            r.call(s.BURST_PRE, ids)
+            r.call(s.BURST_POST, ids)
+        assert np.array_equal(r.out.cpu().numpy(), r.x)
+        for flags in (0, s.FLAG_PROCESS_PACKET):
+            r = Int32Ring(P, cuda, srv, seed=P + 1)
+            r.call(s.BURST_PRE, [0, 1])
+            sent = r.call(s.BURST_EXCHANGE, [0, 1], W=3, flags=flags)
+            last = r.call(s.BURST_EXCHANGE, [2, 3], W=3, flags=flags)
+            x3 = (r.x.astype(np.int64) * 3).astype(np.int32) if flags else r.x
+            assert np.array_equal(r.out.cpu().numpy(), x3)
+            if flags:
+                assert np.array_equal(O.bswap32(last), (O.bswap32(sent).astype(np.uint64) * 3 % (1 << 32)))
+            else:
+                assert np.array_equal(last, sent)
+    finally:
+        if srv is not None:
+            srv.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [64, 1024])
+def test_server_pre_and_post_equal_the_launched_bursts(cuda, P):
+    """FLOAT32 through the burst server with ops PRE and POST (the other
+    server tests run PRE and EXCHANGE): the packet loop over a pinned ring,
+    once with launched bursts and once with submit(BURST_PRE / BURST_POST).
+    Exponent bytes, payload words, whole slots as sent (stale tails included),
+    recv_exps and the output are equal bit for bit, and equal the oracle's
+    packet stream."""
+    s = sw()
+    W, n = 2, partial_last_block(P)
+    x = O.splitmix_normal(P, n) * np.float32(1.5)
+    pe, pp, ref_out, b = O.dummy_packet_stream(x, P=P, batch_max=2, num_workers=W)
+    assert b == 2
+    got = []
+    for route in ("launch", "server"):
+        srv = s.BurstServer(P) if route == "server" else None
+        more = {}
+        try:
+            ce, cp, out, _ = run_bursts(x, P, W, 2, "pinned", cuda, np.random.default_rng(P), srv=srv, more=more)
+        finally:
+            if srv is not None:
+                srv.close()
+        assert np.array_equal(ce, pe), route
+        assert np.array_equal(cp, pp.view(np.uint32)), route
+        assert np.array_equal(out.view(np.uint32), ref_out.view(np.uint32)), route
+        assert np.array_equal(more["recv"], pe[:more["recv"].size]), route
+        got.append((ce, cp, more["slots"], more["recv"], out.view(np.uint32)))
+    for a, c in zip(*got):
+        assert np.array_equal(a, c)
+
+
+@pytest.mark.gpu
+def test_server_refuses_a_null_slice_pointer_and_goes_on(cuda):
+    """The rule of the launched entry points through sml_burst_server_submit:
+    PRE needs `in`, POST needs `out`, EXCHANGE needs both; a refused burst
+    leaves the server able to answer the next valid one."""
+    import torch
+    s = sw()
+    P, W, b = 64, 2, 2
+    n = partial_last_block(P)
+    x = O.splitmix_normal(23, n)
+    xd = torch.from_numpy(x).to(cuda)
+    out = torch.zeros(n, device=cuda)
+    recv = torch.zeros(O.num_blocks(n, P), dtype=torch.int8, device=cuda)
+    rings = torch.full((2, b * P), SLOT_FILL, dtype=torch.int32, device=cuda)
+    extras = torch.zeros(2, b * 2, dtype=torch.uint8, device=cuda)
+
+    def burst(k):
+        return s.packet_burst(xd, out, P, W, b, recv, [0, 1], [rings[k].data_ptr() + q * P * 4 for q in (0, 1)],
+                              [extras[k].data_ptr() + q * 2 for q in (0, 1)])
+
+    srv = s.BurstServer(P)
+    try:
+        for op, null in ((s.BURST_PRE, "in_"), (s.BURST_POST, "out"), (s.BURST_EXCHANGE, "in_"),
+                         (s.BURST_EXCHANGE, "out")):
+            bt = burst(0)
+            setattr(bt, null, None)
+            with pytest.raises(s.SwitchMLError) as e:
+                srv.submit(op, bt)
+            assert e.value.status == s.SML_ERR_INVALID_ARG, (op, null)
+        srv.submit(s.BURST_PRE, burst(0))
+    finally:
+        srv.close()
+    s.preprocess_burst(burst(1))
+    torch.cuda.synchronize()
+    assert np.array_equal(extras[0].cpu().numpy(), extras[1].cpu().numpy())
+    assert np.array_equal(extras[0].cpu().numpy()[::2].view(np.int8), O.exponents(x, P)[:b])
+    assert np.array_equal(rings[0].cpu().numpy(), rings[1].cpu().numpy())
