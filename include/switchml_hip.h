@@ -212,8 +212,11 @@ sml_status_t sml_switch_aggregate(const int32_t* const* d_payloads, const int8_t
  * sml_copy_segments_typed (with sml_copy_segments, below).  A 16-bit slice's RDMA messages need no entry point of
  * their own: sml_quantize_pack_typed at packet_numel = msg_numel gives the
  * message payloads and sml_rdma_imm on its exponent plane the immediates.
- * The burst entry points and sml_roundtrip_loopback_batch take no 16-bit type
- * (a burst whose data_type is one returns SML_ERR_UNSUPPORTED). */
+ * Per-packet bursts of a 16-bit slice go through sml_preprocess_burst_typed /
+ * sml_postprocess_burst_typed / sml_exchange_burst_typed (with the bursts,
+ * below).  The untyped burst entry points, the burst server and
+ * sml_roundtrip_loopback_batch take no 16-bit type (a burst whose data_type
+ * is one returns SML_ERR_UNSUPPORTED there). */
 sml_status_t sml_exponents_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
                                  uint32_t packet_numel, int8_t* d_exps, void* stream);
 sml_status_t sml_quantize_pack_typed(const void* d_in, sml_data_type_t data_type, uint64_t numel,
@@ -334,8 +337,8 @@ sml_status_t sml_release_to_peers(void* stream);
  * q + b only after receiving q).  Flags: SML_FLAG_ROUND_RNE. */
 #define SML_MAX_BURST 64
 typedef struct {
-    const float* in;          /* the job slice (int32 words for INT32) */
-    float* out;
+    const float* in;          /* the job slice (int32 words for INT32; elements of data_type under */
+    float* out;               /* the sml_*_burst_typed entry points, below: a C caller casts)      */
     uint64_t numel;
     uint32_t packet_numel;    /* P */
     uint16_t num_workers;     /* W */
@@ -367,6 +370,32 @@ sml_status_t sml_postprocess_burst(const sml_packet_burst* burst, void* stream);
 #define SML_FLAG_PROCESS_PACKET 0x8u
 sml_status_t sml_exchange_burst(const sml_packet_burst* burst, void* stream);
 
+/* The three burst entry points for a slice of any type: the same struct, with
+ * `in` / `out` pointing at elements of data_type (a C caller casts its
+ * 16-bit pointers to const float* / float*; the struct keeps its layout).
+ *   SML_FLOAT32 / SML_INT32: the untyped entry point, exactly — forwarded
+ *     before any check of the typed function's own, so status and bits are
+ *     those of the twin for every argument list.
+ *   SML_FLOAT16 / SML_BFLOAT16: the kernels convert, by the rule of the other
+ *     sml_*_typed entry points: x32 = (float)x (exact) right after a block of
+ *     the slice is loaded, every packet rule above on x32 as for a FLOAT32
+ *     slice (exponent of block q into byte 0 of the extra slot, block q - b
+ *     under the received exponent, only the real words of a partial block,
+ *     recv_exps, SML_FLAG_PROCESS_PACKET, SML_FLAG_ROUND_RNE), the
+ *     dequantized fp32 value narrowed to the type with round to nearest even
+ *     right before the store.  B = ceil(numel / P) and B + b packets, as for
+ *     FLOAT32; packet buffers, extra slots and recv_exps are byte for byte
+ *     those of a FLOAT32 slice holding the widened values.  `in` and `out`
+ *     need 2-byte alignment only; no byte outside [in, in + 2 numel) is read,
+ *     none outside [out, out + 2 numel) written; in == out is allowed.  The
+ *     argument rules are the FLOAT32 ones: for one argument list every status
+ *     equals that of data_type = SML_FLOAT32.
+ *   Any other data_type: SML_ERR_UNSUPPORTED.
+ * The burst server (below) is not typed: a 16-bit burst takes launches. */
+sml_status_t sml_preprocess_burst_typed(const sml_packet_burst* burst, void* stream);
+sml_status_t sml_postprocess_burst_typed(const sml_packet_burst* burst, void* stream);
+sml_status_t sml_exchange_burst_typed(const sml_packet_burst* burst, void* stream);
+
 /* A persistent burst server, for packet buffers in HOST memory (a NIC's
  * mbuf pool in pinned memory): there a burst launch costs a launch, PCIe
  * round trips and a host synchronisation, ≈ 20 µs per burst (DESIGN.md §9
@@ -384,7 +413,9 @@ sml_status_t sml_exchange_burst(const sml_packet_burst* burst, void* stream);
  * caller stops it between job slices.
  * packet_numel and SML_FLAG_ROUND_RNE are fixed per server (a burst with
  * other values is refused); one server per calling thread; the current
- * device is the server's. */
+ * device is the server's.  FLOAT32 and INT32 slices only: a burst whose
+ * data_type is SML_FLOAT16 / SML_BFLOAT16 returns SML_ERR_UNSUPPORTED (such a
+ * slice goes through the sml_*_burst_typed launches). */
 typedef struct sml_burst_server sml_burst_server;
 #define SML_BURST_PRE 0u
 #define SML_BURST_POST 1u

@@ -84,6 +84,7 @@ bool Config::LoadFromString(const std::string& ini) {
         else if (full == "backend.hip.mode") backend_.hip.mode = val;
         else if (full == "backend.hip.packet_ring") backend_.hip.packet_ring = val;
         else if (full == "backend.hip.burst_server") backend_.hip.burst_server = parse_bool(val);
+        else if (full == "backend.hip.half_packets") backend_.hip.half_packets = parse_bool(val);
         else if (full == "backend.hip.batch_jobs") backend_.hip.batch_jobs = parse_uint<uint32_t>(full, val, 0xffffffffull);
         else if (full == "backend.hip.coalesce_us") backend_.hip.coalesce_us = parse_uint<uint32_t>(full, val, 1000000ull);
         else if (full == "backend.hip.vcl") backend_.hip.vcl = parse_bool(val);
@@ -166,6 +167,7 @@ std::string Config::ToString() const {
       << "\n\n[backend.hip]\ndevice = " << backend_.hip.device << "\nmode = " << backend_.hip.mode
       << "\npacket_ring = " << backend_.hip.packet_ring
       << "\nburst_server = " << (backend_.hip.burst_server ? "true" : "false")
+      << "\nhalf_packets = " << (backend_.hip.half_packets ? "true" : "false")
       << "\nbatch_jobs = " << backend_.hip.batch_jobs
       << "\ncoalesce_us = " << backend_.hip.coalesce_us
       << "\nvcl = " << (backend_.hip.vcl ? "true" : "false")

@@ -59,6 +59,14 @@ struct HipBackendConfig {
     // one resident workgroup polling a doorbell) instead of one launch and a
     // host synchronisation per burst; the server runs for the job slice.
     bool burst_server = false;
+    // FLOAT16 / BFLOAT16 jobs under mode = packet: false = such a job is
+    // refused by the packet loop's first burst hook (it ends FAILED, the tensor
+    // untouched); true = the per-LTU and burst hooks take such a slice, the
+    // kernels converting (sml_*_burst_typed: widened as a block is read,
+    // narrowed as it is written, the packets those of the widened FLOAT32
+    // slice).  Such a slice takes launches: burst_server serves FLOAT32 and
+    // INT32 slices only.
+    bool half_packets = false;
     // mode = fused, loopback switch, no simulated wire: ONE worker thread
     // takes every slice of up to batch_jobs queued jobs (at most
     // SML_MAX_BATCH_SLICES slices) and runs them in one call, one kernel
@@ -125,14 +133,16 @@ class Config {
     void Validate();
     // Whether this configuration runs FLOAT16 / BFLOAT16 jobs: the dummy
     // backend's bulk and fused modes convert them inside the kernels (and the
-    // bypass PPP moves no data, whatever the mode), and the in-node switch
-    // exchanges them when backend.xgmi.half_types is set (it needs the HIP
-    // PPP: Validate); mode = packet and backend = xgmi without half_types
-    // refuse such a job, which then ends FAILED.
+    // bypass PPP moves no data, whatever the mode), its packet mode when
+    // backend.hip.half_packets is set, and the in-node switch exchanges them
+    // when backend.xgmi.half_types is set (it needs the HIP PPP: Validate);
+    // mode = packet without half_packets and backend = xgmi without
+    // half_types refuse such a job, which then ends FAILED.
     bool RunsHalfTypes() const {
         if (general_.backend == "xgmi") return backend_.xgmi.half_types && general_.prepostprocessor != "bypass";
-        return general_.backend == "dummy" && (general_.prepostprocessor == "bypass" ||
-                                               backend_.hip.mode == "bulk" || backend_.hip.mode == "fused");
+        return general_.backend == "dummy" &&
+               (general_.prepostprocessor == "bypass" || backend_.hip.mode == "bulk" || backend_.hip.mode == "fused" ||
+                (backend_.hip.mode == "packet" && backend_.hip.half_packets));
     }
     std::string ToString() const;
     void PrintConfig() const;

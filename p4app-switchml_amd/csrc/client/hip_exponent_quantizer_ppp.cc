@@ -65,14 +65,15 @@ uint64_t HipExponentQuantizerPPP::SetupJobSlice(JobSlice* job_slice) {
 bool HipExponentQuantizerPPP::NeedsExtraBatch() { return IsFloatType(job_slice_->slice.data_type); }
 
 // FLOAT16 / BFLOAT16 slices run through the bulk hooks and the fused round
-// trip only; every per-packet path refuses them by name rather than run them
-// as another type.
+// trip, and through the per-packet paths under backend.hip.half_packets (the
+// typed burst and plane entry points convert); without that key every
+// per-packet path refuses them by name rather than run them as another type.
 void HipExponentQuantizerPPP::refuse_half(const char* call) const {
     const DataType dt = job_slice_->slice.data_type;
-    if (IsHalfType(dt))
+    if (IsHalfType(dt) && !config_.backend_.hip.half_packets)
         throw SwitchMLFatal(std::string(call) + ": " + DataTypeName(dt) +
-                            " jobs are not supported by the per-LTU and burst hooks (backend.hip.mode = packet); "
-                            "set backend.hip.mode = bulk or fused");
+                            " jobs are not supported by the per-LTU and burst hooks (backend.hip.mode = packet) "
+                            "without backend.hip.half_packets = true; set it, or backend.hip.mode = bulk or fused");
 }
 
 void HipExponentQuantizerPPP::CleanupJobSlice() {
@@ -143,15 +144,18 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
     const uint32_t P = (uint32_t)ltu_numel_;
     ensure_single_buffers();
     bool sync = false;
-    if (s.data_type == FLOAT32) {
+    if (IsFloatType(s.data_type)) {   // FLOAT32 forwards to sml_quantize_pack / sml_exponents
+        const sml_data_type_t dt = SmlFloatType(s.data_type);
+        const char* in = static_cast<const char*>(s.in_ptr);
+        const size_t esize = DataTypeSize(s.data_type);
         if (ltu_id >= batch_num_ltus_) {
             const uint64_t k = ltu_id - batch_num_ltus_;
             const uint64_t off = k * P, n = std::min<uint64_t>(P, s.numel - off);
             // the kernel writes all P words of the block; the reference writes
             // only the n real ones (ppp.cc:102-109), so a partial block is staged
             sync |= write_packet(entries_ptr, d_stage_, n * 4, n == P, [&](int32_t* dst) {
-                check(sml_quantize_pack(static_cast<const float*>(s.in_ptr) + off, n, P, config_.general_.num_workers,
-                                        d_recv_exps_ + k, dst, nullptr, round_flags_, stream_),
+                check(sml_quantize_pack_typed(in + off * esize, dt, n, P, config_.general_.num_workers,
+                                              d_recv_exps_ + k, dst, nullptr, round_flags_, stream_),
                       "sml_quantize_pack");
             });
         }
@@ -159,7 +163,7 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
             const uint64_t off = ltu_id * P, n = std::min<uint64_t>(P, s.numel - off);
             // one byte: the int8 exponent in byte 0 of the extra-info slot (byte 1 untouched)
             sync |= write_packet(extra_info, d_stage_exp_, 1, true, [&](int8_t* dst) {
-                check(sml_exponents(static_cast<const float*>(s.in_ptr) + off, n, P, dst, stream_), "sml_exponents");
+                check(sml_exponents_typed(in + off * esize, dt, n, P, dst, stream_), "sml_exponents");
             });
         }
     } else if (s.data_type == INT32) {
@@ -183,12 +187,14 @@ void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_
     const uint32_t P = (uint32_t)ltu_numel_;
     ensure_single_buffers();
     bool sync = false;
-    if (s.data_type == FLOAT32) {
+    if (IsFloatType(s.data_type)) {   // FLOAT32 forwards to sml_dequantize
         if (ltu_id >= batch_num_ltus_) {
             const uint64_t k = ltu_id - batch_num_ltus_;
             const uint64_t off = k * P, n = std::min<uint64_t>(P, s.numel - off);
-            check(sml_dequantize(read_packet(entries_ptr, n * 4, sync), d_recv_exps_ + k, n, P,
-                                 config_.general_.num_workers, static_cast<float*>(s.out_ptr) + off, 0, stream_),
+            check(sml_dequantize_typed(read_packet(entries_ptr, n * 4, sync), d_recv_exps_ + k, n, P,
+                                       config_.general_.num_workers,
+                                       static_cast<char*>(s.out_ptr) + off * DataTypeSize(s.data_type),
+                                       SmlFloatType(s.data_type), 0, stream_),
                   "sml_dequantize");
         }
         if (ltu_id < total_main_num_ltus_) {
@@ -225,16 +231,17 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
         uint32_t op;
         sml_status_t (*launch)(const sml_packet_burst*, void*);
     };
+    // the typed entry points: a FLOAT32 or INT32 burst is forwarded to the untyped twin
     static constexpr Names kNames[] = {   // by BurstKind
-        {"PreprocessBurst", "sml_preprocess_burst", SML_BURST_PRE, sml_preprocess_burst},
-        {"PostprocessBurst", "sml_postprocess_burst", SML_BURST_POST, sml_postprocess_burst},
-        {"PostprocessReuseBurst", "sml_exchange_burst", SML_BURST_EXCHANGE, sml_exchange_burst},
-        {"ProcessPostprocessReuseBurst", "sml_exchange_burst", SML_BURST_EXCHANGE, sml_exchange_burst},
+        {"PreprocessBurst", "sml_preprocess_burst", SML_BURST_PRE, sml_preprocess_burst_typed},
+        {"PostprocessBurst", "sml_postprocess_burst", SML_BURST_POST, sml_postprocess_burst_typed},
+        {"PostprocessReuseBurst", "sml_exchange_burst", SML_BURST_EXCHANGE, sml_exchange_burst_typed},
+        {"ProcessPostprocessReuseBurst", "sml_exchange_burst", SML_BURST_EXCHANGE, sml_exchange_burst_typed},
     };
     const Names& as = kNames[static_cast<int>(kind)];
     refuse_half(as.hook);
     const Tensor& s = job_slice_->slice;
-    const bool flt = s.data_type == FLOAT32;
+    const bool flt = IsFloatType(s.data_type);
     const uint64_t total = total_main_num_ltus_ + (flt ? batch_num_ltus_ : 0);
     ensure_single_buffers();
     // one pool per slice: the query is cached for the slice (SetupJobSlice resets it)
@@ -284,17 +291,18 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
     };
     const bool exchange = as.op == SML_BURST_EXCHANGE;
     sml_packet_burst b{};
-    b.in = static_cast<const float*>(s.in_ptr);
+    b.in = static_cast<const float*>(s.in_ptr);   // elements of data_type (the typed entry points)
     b.out = static_cast<float*>(s.out_ptr);
     b.numel = s.numel;
     b.packet_numel = (uint32_t)ltu_numel_;
     b.num_workers = config_.general_.num_workers;
-    b.data_type = flt ? SML_FLOAT32 : SML_INT32;
+    b.data_type = flt ? SmlFloatType(s.data_type) : SML_INT32;
     // the exchange needs the window for INT32 too (the next packet is q + b)
     b.batch_num_ltus = flt || exchange ? batch_num_ltus_ : 0;
     b.recv_exps = d_recv_exps_;
     b.flags = (kind == BurstKind::kProcessExchange ? SML_FLAG_PROCESS_PACKET : 0u) | round_flags_;
-    const bool serve = m.host() && config_.backend_.hip.burst_server;
+    // the server runs FLOAT32 and INT32 slices only: a 16-bit slice takes launches
+    const bool serve = m.host() && config_.backend_.hip.burst_server && !IsHalfType(s.data_type);
     if (serve && !server_) {
         check(sml_burst_server_create((uint32_t)ltu_numel_, round_flags_, 100, &server_), "sml_burst_server_create");
     }
@@ -332,7 +340,7 @@ void HipExponentQuantizerPPP::PostprocessBurst(uint32_t n, const uint64_t* ltu_i
 void HipExponentQuantizerPPP::PostprocessReuseBurst(uint32_t n, const uint64_t* ltu_ids, void* const* entries,
                                                     void* const* extras, uint64_t batch, uint64_t total_ltus) {
     refuse_half("PostprocessReuseBurst");
-    const bool flt = job_slice_->slice.data_type == FLOAT32;
+    const bool flt = IsFloatType(job_slice_->slice.data_type);
     if (batch != batch_num_ltus_ || total_ltus != total_main_num_ltus_ + (flt ? batch_num_ltus_ : 0))
         throw SwitchMLFatal("PostprocessReuseBurst: batch / total_ltus differ from the slice's b / B (+ b)");
     burst(BurstKind::kExchange, n, ltu_ids, entries, extras);

@@ -43,12 +43,14 @@ class HipExponentQuantizerPPP : public PrePostProcessor {
     void CleanupJobSlice() override;
 
     // One launch per burst of up to SML_MAX_BURST packets (sml_preprocess_burst
-    // / sml_postprocess_burst): the packet buffers must be device-addressable
-    // (HBM or pinned host memory); pageable ones take the per-packet path.
+    // / sml_postprocess_burst, through their _typed forms): the packet buffers
+    // must be device-addressable (HBM or pinned host memory); pageable ones
+    // take the per-packet path.  A FLOAT16 / BFLOAT16 slice runs under
+    // backend.hip.half_packets and is refused by name without it.
     void PreprocessBurst(uint32_t n, const uint64_t* ltu_ids, void* const* entries, void* const* extras) override;
     void PostprocessBurst(uint32_t n, const uint64_t* ltu_ids, void* const* entries, void* const* extras) override;
     // One launch per SML_MAX_BURST received packets (sml_exchange_burst);
-    // batch / total_ltus must be this slice's b and B (+ b for FLOAT32).
+    // batch / total_ltus must be this slice's b and B (+ b for a float type).
     void PostprocessReuseBurst(uint32_t n, const uint64_t* ltu_ids, void* const* entries, void* const* extras,
                                uint64_t batch, uint64_t total_ltus) override;
     // The same with the dummy backend's ProcessPacket (x num_workers,
@@ -80,7 +82,7 @@ class HipExponentQuantizerPPP : public PrePostProcessor {
   private:
     void check(int status, const char* what) const;
     void refuse_per_ltu(const char* call) const;
-    void refuse_half(const char* call) const;   // throws for a FLOAT16 / BFLOAT16 slice
+    void refuse_half(const char* call) const;   // throws for a FLOAT16 / BFLOAT16 slice without backend.hip.half_packets
     void preprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);
     void postprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);
     void ensure_single_buffers();

@@ -98,7 +98,9 @@ struct WorkerState {
 };
 
 // DummyWorkerThread's per-packet loop (dummy_worker_thread.cc:86-177) with
-// in-order delivery over a device-resident ring of b packets.
+// in-order delivery over a device-resident ring of b packets.  The ring holds
+// wire words, whatever the slice's element type (FLOAT16 / BFLOAT16 slices
+// under backend.hip.half_packets: the PPP's hooks convert).
 void run_packet_loop(HipExponentQuantizerPPP& ppp, const Config& cfg, WorkerState& ws, bool extra_batch) {
     const uint64_t P = ppp.ltu_numel();
     const uint64_t B = ppp.total_main_num_ltus();
@@ -170,10 +172,11 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
     Tensor& t = js.slice;
     const std::string& mode = cfg.backend_.hip.mode;
     // FLOAT16 / BFLOAT16: the bulk hooks and the fused round trip convert
-    // inside the kernels, and so does the in-node switch under
-    // backend.xgmi.half_types; the per-packet loop's first burst hook and the
-    // in-node switch without that key (XgmiSwitch::AllReduceSlice) throw for
-    // such a slice, before anything is written, rather than run it as
+    // inside the kernels, and so do the in-node switch under
+    // backend.xgmi.half_types and the per-packet loop under
+    // backend.hip.half_packets; without its key the per-packet loop's first
+    // burst hook, or the in-node switch (XgmiSwitch::AllReduceSlice), throws
+    // for such a slice, before anything is written, rather than run it as
     // another type
     const size_t bytes = t.numel * DataTypeSize(t.data_type);
     // Device tensors are used in place; pinned host tensors too, through

@@ -29,6 +29,13 @@
 // burst's, which does both for a received packet in one wave (post of q,
 // then pre of q + b into the same buffer: one launch per rx burst).
 //
+// FLOAT16 / BFLOAT16 slices (the sml_*_burst_typed entry points): a block of
+// the slice is widened to fp32 bits as it is loaded and the dequantized fp32
+// values are narrowed (round to nearest even) as they are stored; everything
+// between — wire words, exponents, scales — is the FLOAT32 packet, byte for
+// byte.  The slice's element type is the policy E of the two slice-side
+// phases (SliceWords, Slice16<H>), nothing else knows it.
+//
 // Each rule is written once.  Device: the phases of one packet (PacketLanes,
 // real_words, load_words / store_words for packets and blocks of the slice,
 // store_block_exponent, pack_block, unpack_block, payload_of), which the three
@@ -83,23 +90,78 @@ __device__ __forceinline__ void store_group(uint32_t* buf, uint64_t j, uint64_t 
     }
 }
 
-// Words [0, n) of a packet buffer <-> w.
-template <int P, int U>
-__device__ __forceinline__ void load_words(PacketLanes<P> g, const uint32_t* buf, uint64_t n, uint32_t (&w)[U][4]) {
+// What a buffer's elements are to load_group / store_group: the words
+// themselves (packet buffers; FLOAT32 and INT32 slices, whose elements are
+// their bits), or 16-bit floats held as fp32 bits in registers (FLOAT16 /
+// BFLOAT16 slices).  is_float: whether the slice takes the float rules — a
+// 16-bit instance has no INT32 branch.
+struct SliceWords {
+    typedef uint32_t raw;
+    static __device__ __forceinline__ bool is_float(const sml_packet_burst& a) { return a.data_type == SML_FLOAT32; }
+    static __device__ __forceinline__ void load_group(const raw* buf, uint64_t j, uint64_t n, uint32_t (&v)[4]) {
+        sml::load_group(buf, j, n, v);
+    }
+    static __device__ __forceinline__ void store_group(raw* buf, uint64_t j, uint64_t n, const uint32_t (&v)[4]) {
+        sml::store_group(buf, j, n, v);
+    }
+};
+
+// A lane's four elements are one 8-byte access through the 2-byte-aligned
+// vector type where the group is whole (a slice starts at any element),
+// single elements in the group that n cuts; widened (exact) right after the
+// load, narrowed (round to nearest even) right before the store.
+template <int H>
+struct Slice16 {
+    typedef uint16_t raw;
+    static __device__ __forceinline__ bool is_float(const sml_packet_burst&) { return true; }
+    static __device__ __forceinline__ void load_group(const raw* buf, uint64_t j, uint64_t n, uint32_t (&v)[4]) {
+        if (j + 4 <= n) {
+            const h4a q = *reinterpret_cast<const h4a*>(buf + j);
+            v[0] = __float_as_uint(widen16<H>(q.x)), v[1] = __float_as_uint(widen16<H>(q.y));
+            v[2] = __float_as_uint(widen16<H>(q.z)), v[3] = __float_as_uint(widen16<H>(q.w));
+        } else {
 #pragma unroll
-    for (int u = 0; u < U; u++) load_group(buf, g.j(u), n, w[u]);
+            for (int t = 0; t < 4; t++) v[t] = j + t < n ? __float_as_uint(widen16<H>(buf[j + t])) : 0u;
+        }
+    }
+    static __device__ __forceinline__ void store_group(raw* buf, uint64_t j, uint64_t n, const uint32_t (&v)[4]) {
+        if (j + 4 <= n) {
+            *reinterpret_cast<h4a*>(buf + j) =
+                h4a{narrow16<H>(__uint_as_float(v[0])), narrow16<H>(__uint_as_float(v[1])),
+                    narrow16<H>(__uint_as_float(v[2])), narrow16<H>(__uint_as_float(v[3]))};
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                if (j + t < n) buf[j + t] = narrow16<H>(__uint_as_float(v[t]));
+        }
+    }
+};
+
+// Elements [0, n) of a buffer <-> w: a packet buffer's words (E = SliceWords),
+// or a block of the slice as fp32 bits.
+template <class E = SliceWords, int P, int U>
+__device__ __forceinline__ void load_words(PacketLanes<P> g, const typename E::raw* buf, uint64_t n,
+                                           uint32_t (&w)[U][4]) {
+#pragma unroll
+    for (int u = 0; u < U; u++) E::load_group(buf, g.j(u), n, w[u]);
 }
 
-template <int P, int U>
-__device__ __forceinline__ void store_words(PacketLanes<P> g, uint32_t* buf, uint64_t n, const uint32_t (&w)[U][4]) {
+template <class E = SliceWords, int P, int U>
+__device__ __forceinline__ void store_words(PacketLanes<P> g, typename E::raw* buf, uint64_t n,
+                                            const uint32_t (&w)[U][4]) {
 #pragma unroll
-    for (int u = 0; u < U; u++) store_group(buf, g.j(u), n, w[u]);
+    for (int u = 0; u < U; u++) E::store_group(buf, g.j(u), n, w[u]);
 }
 
-// Block k of the slice as words (FLOAT32: its bits), for load_words.
-template <int P>
-__device__ __forceinline__ const uint32_t* block_words(const sml_packet_burst& a, uint64_t k) {
-    return reinterpret_cast<const uint32_t*>(a.in) + k * P;
+// Block k of the slice (FLOAT32: its bits as words), for load_words<E>.
+template <class E, int P>
+__device__ __forceinline__ const typename E::raw* block_words(const sml_packet_burst& a, uint64_t k) {
+    return reinterpret_cast<const typename E::raw*>(a.in) + k * P;
+}
+// Block k of the output, for unpack_block<E>.
+template <class E, int P>
+__device__ __forceinline__ typename E::raw* block_out(const sml_packet_burst& a, uint64_t k) {
+    return reinterpret_cast<typename E::raw*>(a.out) + k * P;
 }
 __device__ __forceinline__ f4 as_f4(const uint32_t (&v)[4]) {
     return mkf4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
@@ -134,17 +196,18 @@ __device__ __forceinline__ void pack_block(PacketLanes<P> g, bool flt, const uin
     }
 }
 
-// Words [0, n) of w into the n words of a block of the output: dequantized
-// with scale s (FLOAT32), or byte-swapped (INT32).
-template <int P, int U>
+// Words [0, n) of w into the n elements of a block of the output: dequantized
+// with scale s (a float type; a 16-bit one narrowed by E's store), or
+// byte-swapped (INT32).
+template <class E, int P, int U>
 __device__ __forceinline__ void unpack_block(PacketLanes<P> g, bool flt, const uint32_t (&w)[U][4], float s, uint64_t n,
-                                             uint32_t* out) {
+                                             typename E::raw* out) {
 #pragma unroll
     for (int u = 0; u < U; u++) {
         uint32_t v[4];   // every word of the group converted, whole group or not: four divisions in flight
 #pragma unroll
         for (int t = 0; t < 4; t++) v[t] = flt ? __float_as_uint(dequantize1(bswap(w[u][t]), s)) : bswap(w[u][t]);
-        store_group(out, g.j(u), n, v);
+        E::store_group(out, g.j(u), n, v);
     }
 }
 
@@ -160,39 +223,39 @@ __device__ __forceinline__ Payload payload_of(const sml_packet_burst& a, bool fl
 // PreprocessSingle of packet q: its block into the packet with the scale of
 // the exponent received for that block (recv_exps, in memory), only the real
 // words written; the exponent of block q into the extra slot (FLOAT32, q < B).
-template <int P, bool RNE>
+template <class E, int P, bool RNE>
 __device__ __forceinline__ void preprocess_one(const sml_packet_burst& a, uint32_t i) {
     const PacketLanes<P> g{};
     constexpr int U = PacketLanes<P>::U;
     const uint64_t q = a.pkt_ids[i];
     const uint64_t B = (a.numel + P - 1) / P;
-    const bool flt = a.data_type == SML_FLOAT32;
+    const bool flt = E::is_float(a);
     const Payload pay = payload_of(a, flt, q);
     uint32_t x[U][4];
     if (pay.on) {
         const uint64_t n = real_words<P>(a, pay.k);
         const int e = flt ? (int)a.recv_exps[pay.k] : 0;   // asked for ahead of the block: one wait for both
         uint32_t w[U][4] = {};
-        load_words(g, block_words<P>(a, pay.k), n, x);
+        load_words<E>(g, block_words<E, P>(a, pay.k), n, x);
         const float s = flt ? scale_for(a.num_workers, e) : 0.0f;
         pack_block<P, RNE>(g, flt, x, s, n, w);
         store_words(g, static_cast<uint32_t*>(a.entries[i]), n, w);
     }
     if (flt && q < B) {
-        load_words(g, block_words<P>(a, q), real_words<P>(a, q), x);
+        load_words<E>(g, block_words<E, P>(a, q), real_words<P>(a, q), x);
         store_block_exponent(g, x, a.extras[i]);
     }
 }
 
 // PostprocessSingle of packet q: its block out of the packet into the slice
 // output; the packet's exponent byte kept as block q's received exponent.
-template <int P>
+template <class E, int P>
 __device__ __forceinline__ void postprocess_one(const sml_packet_burst& a, uint32_t i) {
     const PacketLanes<P> g{};
     constexpr int U = PacketLanes<P>::U;
     const uint64_t q = a.pkt_ids[i];
     const uint64_t B = (a.numel + P - 1) / P;
-    const bool flt = a.data_type == SML_FLOAT32;
+    const bool flt = E::is_float(a);
     const Payload pay = payload_of(a, flt, q);
     if (pay.on) {
         const uint64_t n = real_words<P>(a, pay.k);
@@ -200,7 +263,7 @@ __device__ __forceinline__ void postprocess_one(const sml_packet_burst& a, uint3
         uint32_t w[U][4];
         load_words(g, static_cast<const uint32_t*>(a.entries[i]), n, w);
         const float s = flt ? scale_for(a.num_workers, e) : 0.0f;
-        unpack_block(g, flt, w, s, n, reinterpret_cast<uint32_t*>(a.out) + pay.k * P);
+        unpack_block<E>(g, flt, w, s, n, block_out<E, P>(a, pay.k));
     }
     if (flt && q < B && g.lane == 0) a.recv_exps[q] = *static_cast<const int8_t*>(a.extras[i]);
 }
@@ -221,14 +284,14 @@ __device__ __forceinline__ void postprocess_one(const sml_packet_burst& a, uint3
 // Every load of the packet is waited for before its buffer is written: the
 // reads and the writes of one buffer may cross PCIe (pinned mbufs), where a
 // posted write may overtake an outstanding read.
-template <int P, bool RNE, bool PROC>
+template <class E, int P, bool RNE, bool PROC>
 __device__ __forceinline__ void exchange_one(const sml_packet_burst& a, uint32_t i) {
     const PacketLanes<P> g{};
     constexpr int U = PacketLanes<P>::U;
     const uint64_t q = a.pkt_ids[i];
     const uint64_t B = (a.numel + P - 1) / P;
     const uint64_t b = a.batch_num_ltus;
-    const bool flt = a.data_type == SML_FLOAT32;
+    const bool flt = E::is_float(a);
     uint32_t* ent = static_cast<uint32_t*>(a.entries[i]);
 
     // what each half touches: post reads words [0, n_post) of the packet
@@ -245,8 +308,8 @@ __device__ __forceinline__ void exchange_one(const sml_packet_burst& a, uint32_t
     load_words(g, ent, PROC ? P : n_post, w);
     const int e_recv = flt && q < B ? (int)*static_cast<const int8_t*>(a.extras[i]) : 0;
     const int e_post = flt && post.on ? (int)a.recv_exps[post.k] : 0;
-    load_words(g, block_words<P>(a, n_pre ? k_pre : 0), n_pre, xq);
-    load_words(g, block_words<P>(a, n_exp ? q + b : 0), n_exp, xe);
+    load_words<E>(g, block_words<E, P>(a, n_pre ? k_pre : 0), n_pre, xq);
+    load_words<E>(g, block_words<E, P>(a, n_exp ? q + b : 0), n_exp, xe);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
     // ---- ProcessPacket, postprocess
@@ -257,7 +320,7 @@ __device__ __forceinline__ void exchange_one(const sml_packet_burst& a, uint32_t
 #pragma unroll
             for (int t = 0; t < 4; t++) w[u][t] = bswap(bswap(w[u][t]) * W);
     }
-    unpack_block(g, flt, w, flt ? scale_for(W, e_post) : 0.0f, n_post, reinterpret_cast<uint32_t*>(a.out) + post.k * P);
+    unpack_block<E>(g, flt, w, flt ? scale_for(W, e_post) : 0.0f, n_post, block_out<E, P>(a, post.k));
     if (flt && q < B && g.lane == 0) a.recv_exps[q] = (int8_t)e_recv;
 
     // ---- preprocess of q + b into the same buffer: its words are the new
@@ -267,23 +330,23 @@ __device__ __forceinline__ void exchange_one(const sml_packet_burst& a, uint32_t
     if (n_exp) store_block_exponent(g, xe, a.extras[i]);
 }
 
-// One launch per burst: a wave per packet.
-template <int P, bool RNE>
+// One launch per burst: a wave per packet.  E: the slice's element policy.
+template <class E, int P, bool RNE>
 __global__ __launch_bounds__(kBlockThreads) void k_preprocess_burst(sml_packet_burst a) {
     const uint32_t i = blockIdx.x * kWavesPerBlock + wave_index();
-    if (i < a.count) preprocess_one<P, RNE>(a, i);
+    if (i < a.count) preprocess_one<E, P, RNE>(a, i);
 }
 
-template <int P>
+template <class E, int P>
 __global__ __launch_bounds__(kBlockThreads) void k_postprocess_burst(sml_packet_burst a) {
     const uint32_t i = blockIdx.x * kWavesPerBlock + wave_index();
-    if (i < a.count) postprocess_one<P>(a, i);
+    if (i < a.count) postprocess_one<E, P>(a, i);
 }
 
-template <int P, bool RNE, bool PROC>
+template <class E, int P, bool RNE, bool PROC>
 __global__ __launch_bounds__(kBlockThreads) void k_exchange_burst(sml_packet_burst a) {
     const uint32_t i = blockIdx.x * kWavesPerBlock + wave_index();
-    if (i < a.count) exchange_one<P, RNE, PROC>(a, i);
+    if (i < a.count) exchange_one<E, P, RNE, PROC>(a, i);
 }
 
 // ---- the persistent burst server (include/switchml_hip.h) ----------------
@@ -299,7 +362,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_exchange_burst(sml_packet_bur
 // device memory.  The last workgroup to arrive resets the counter and
 // publishes the burst's sequence number with a system-scope release store;
 // the host submits the next burst only after that, so no workgroup can run
-// ahead into the next burst.  The loop ends on `stop` or after idle_ticks of
+// ahead into the next burst.  FLOAT32 and INT32 slices only (SliceWords): a
+// 16-bit slice never comes here (check_burst refuses it for the server).  The loop ends on `stop` or after idle_ticks of
 // wall clock without a doorbell, so every wave reaches the exit on its own;
 // the host restarts a server that has been idle for half that long before
 // ringing it again, so a doorbell never races an idle exit.
@@ -370,10 +434,10 @@ __global__ __launch_bounds__(kServerThreads) void k_burst_server(ServerCtl* ctl,
         const uint32_t n = sa.count;
         const bool proc = (sa.flags & SML_FLAG_PROCESS_PACKET) != 0;
         for (uint32_t i = blockIdx.x * kWaves + wave_index(); i < n; i += kAllWaves) {
-            if (cmd == SML_BURST_PRE) preprocess_one<P, RNE>(sa, i);
-            else if (cmd == SML_BURST_POST) postprocess_one<P>(sa, i);
-            else if (proc) exchange_one<P, RNE, true>(sa, i);
-            else exchange_one<P, RNE, false>(sa, i);
+            if (cmd == SML_BURST_PRE) preprocess_one<SliceWords, P, RNE>(sa, i);
+            else if (cmd == SML_BURST_POST) postprocess_one<SliceWords, P>(sa, i);
+            else if (proc) exchange_one<SliceWords, P, RNE, true>(sa, i);
+            else exchange_one<SliceWords, P, RNE, false>(sa, i);
         }
         __syncthreads();
         if (tid == 0) {
@@ -392,18 +456,20 @@ __global__ __launch_bounds__(kServerThreads) void k_burst_server(ServerCtl* ctl,
 // Host checks of a burst for op SML_BURST_PRE / POST / EXCHANGE, shared by the
 // launched entry points and the server.  The preprocess reads the slice, the
 // postprocess writes the output, the exchange does both; its packet window b
-// applies to INT32 slices too (the next packet is q + b).
-static sml_status_t check_burst(const sml_packet_burst* a, uint32_t op) {
+// applies to INT32 slices too (the next packet is q + b).  half_ok (the
+// _typed entry points): FLOAT16 / BFLOAT16 pass, under the FLOAT32 rules.
+static sml_status_t check_burst(const sml_packet_burst* a, uint32_t op, bool half_ok = false) {
     const bool window = op == SML_BURST_EXCHANGE;
     if (!a) return SML_ERR_INVALID_ARG;
     if (!valid_packet(a->packet_numel)) return SML_ERR_UNSUPPORTED;
     if (a->count > SML_MAX_BURST || a->num_workers == 0) return SML_ERR_INVALID_ARG;
-    if (a->data_type != SML_FLOAT32 && a->data_type != SML_INT32) return SML_ERR_UNSUPPORTED;
+    const bool half = a->data_type == SML_FLOAT16 || a->data_type == SML_BFLOAT16;
+    if (a->data_type != SML_FLOAT32 && a->data_type != SML_INT32 && !(half && half_ok)) return SML_ERR_UNSUPPORTED;
     if (a->count == 0) return SML_OK;
     if ((op != SML_BURST_POST && !a->in) || (op != SML_BURST_PRE && !a->out)) return SML_ERR_INVALID_ARG;
     const uint64_t P = a->packet_numel;
     const uint64_t B = sml_num_blocks(a->numel, (uint32_t)P);
-    const bool flt = a->data_type == SML_FLOAT32;
+    const bool flt = a->data_type != SML_INT32;
     const uint64_t b = flt || window ? a->batch_num_ltus : 0;
     if ((flt || window) && b > B) return SML_ERR_INVALID_ARG;
     if (window && b == 0) return SML_ERR_INVALID_ARG;
@@ -429,24 +495,46 @@ static sml_status_t check_burst(const sml_packet_burst* a, uint32_t op) {
     return SML_OK;
 }
 
+// The slice's element policy from its sml_data_type_t (checked by check_burst).
+template <class F>
+static void dispatch_slice_type(uint32_t data_type, F&& f) {
+    if (data_type == SML_FLOAT16) f(Slice16<kHalfF16>{});
+    else if (data_type == SML_BFLOAT16) f(Slice16<kHalfBF16>{});
+    else f(SliceWords{});
+}
+
 // One launch for the burst, a wave per packet, on `stream`: the kernel of op
-// for the burst's packet size and the flags that op knows.
-static sml_status_t launch_burst(const sml_packet_burst* burst, uint32_t op, void* stream) {
-    const sml_status_t st = check_burst(burst, op);
+// for the slice's element type, the burst's packet size and the flags that op
+// knows.
+static sml_status_t launch_burst(const sml_packet_burst* burst, uint32_t op, void* stream, bool half_ok = false) {
+    const sml_status_t st = check_burst(burst, op, half_ok);
     if (st != SML_OK || burst->count == 0) return st;
     const sml_packet_burst& a = *burst;
     const dim3 grid((a.count + kWavesPerBlock - 1) / kWavesPerBlock);
     const hipStream_t s = (hipStream_t)stream;
     const bool rne = (a.flags & SML_FLAG_ROUND_RNE) != 0;
     const bool proc = (a.flags & SML_FLAG_PROCESS_PACKET) != 0;
-    dispatch_packet(a.packet_numel, [&](auto Pc) {
-        dispatch_bools([&](auto RNE, auto PROC) {
-            if (op == SML_BURST_PRE) k_preprocess_burst<Pc(), RNE()><<<grid, kBlockThreads, 0, s>>>(a);
-            else if (op == SML_BURST_POST) k_postprocess_burst<Pc()><<<grid, kBlockThreads, 0, s>>>(a);
-            else k_exchange_burst<Pc(), RNE(), PROC()><<<grid, kBlockThreads, 0, s>>>(a);
-        }, rne, proc);
+    dispatch_slice_type(a.data_type, [&](auto Ec) {
+        using E = decltype(Ec);
+        dispatch_packet(a.packet_numel, [&](auto Pc) {
+            dispatch_bools([&](auto RNE, auto PROC) {
+                if (op == SML_BURST_PRE) k_preprocess_burst<E, Pc(), RNE()><<<grid, kBlockThreads, 0, s>>>(a);
+                else if (op == SML_BURST_POST) k_postprocess_burst<E, Pc()><<<grid, kBlockThreads, 0, s>>>(a);
+                else k_exchange_burst<E, Pc(), RNE(), PROC()><<<grid, kBlockThreads, 0, s>>>(a);
+            }, rne, proc);
+        });
     });
     return launch_check();
+}
+
+// The _typed entry points: FLOAT32 / INT32 (and a NULL burst) are the untyped
+// twin's, before any check of their own; the 16-bit types run their instances
+// under the FLOAT32 argument rules; anything else is unsupported.
+static sml_status_t launch_burst_typed(const sml_packet_burst* burst, uint32_t op, void* stream) {
+    if (!burst || burst->data_type == SML_FLOAT32 || burst->data_type == SML_INT32)
+        return launch_burst(burst, op, stream);
+    if (burst->data_type != SML_FLOAT16 && burst->data_type != SML_BFLOAT16) return SML_ERR_UNSUPPORTED;
+    return launch_burst(burst, op, stream, true);
 }
 
 }  // namespace sml
@@ -465,6 +553,18 @@ sml_status_t sml_postprocess_burst(const sml_packet_burst* burst, void* stream) 
 
 sml_status_t sml_exchange_burst(const sml_packet_burst* burst, void* stream) {
     return launch_burst(burst, SML_BURST_EXCHANGE, stream);
+}
+
+sml_status_t sml_preprocess_burst_typed(const sml_packet_burst* burst, void* stream) {
+    return launch_burst_typed(burst, SML_BURST_PRE, stream);
+}
+
+sml_status_t sml_postprocess_burst_typed(const sml_packet_burst* burst, void* stream) {
+    return launch_burst_typed(burst, SML_BURST_POST, stream);
+}
+
+sml_status_t sml_exchange_burst_typed(const sml_packet_burst* burst, void* stream) {
+    return launch_burst_typed(burst, SML_BURST_EXCHANGE, stream);
 }
 
 }  // extern "C"

@@ -193,6 +193,12 @@ def lib():
     L.sml_postprocess_burst.argtypes = [ctypes.POINTER(PacketBurst), vp]
     L.sml_exchange_burst.restype = i32
     L.sml_exchange_burst.argtypes = [ctypes.POINTER(PacketBurst), vp]
+    L.sml_preprocess_burst_typed.restype = i32
+    L.sml_preprocess_burst_typed.argtypes = [ctypes.POINTER(PacketBurst), vp]
+    L.sml_postprocess_burst_typed.restype = i32
+    L.sml_postprocess_burst_typed.argtypes = [ctypes.POINTER(PacketBurst), vp]
+    L.sml_exchange_burst_typed.restype = i32
+    L.sml_exchange_burst_typed.argtypes = [ctypes.POINTER(PacketBurst), vp]
     L.sml_burst_server_create.restype = i32
     L.sml_burst_server_create.argtypes = [u32, u32, u32, ctypes.POINTER(vp)]
     L.sml_burst_server_submit.restype = i32
@@ -579,8 +585,10 @@ def copy_segments_typed(pairs, flags: int = 0, stream=None):
 
 def packet_burst(x, out, packet_numel: int, num_workers: int, batch_num_ltus: int, recv_exps, pkt_ids,
                  entries, extras, flags: int = 0) -> PacketBurst:
-    """A PacketBurst over slice `x` (fp32 or int32 CUDA tensor) and output
-    `out`; entries / extras are device-addressable addresses (ints)."""
+    """A PacketBurst over slice `x` (fp32, fp16, bf16 or int32 CUDA tensor) and
+    output `out`; entries / extras are device-addressable addresses (ints).
+    A 16-bit slice's burst runs through preprocess_burst / postprocess_burst /
+    exchange_burst (the typed entry points), not through a BurstServer."""
     torch = _torch()
     if len(pkt_ids) > MAX_BURST:
         raise ValueError(f"at most {MAX_BURST} packets per burst")
@@ -590,7 +598,7 @@ def packet_burst(x, out, packet_numel: int, num_workers: int, batch_num_ltus: in
     b.numel = x.numel()
     b.packet_numel = packet_numel
     b.num_workers = num_workers
-    b.data_type = 1 if x.dtype == torch.int32 else 0
+    b.data_type = {torch.int32: INT32, torch.float16: FLOAT16, torch.bfloat16: BFLOAT16}.get(x.dtype, FLOAT32)
     b.batch_num_ltus = batch_num_ltus
     b.recv_exps = recv_exps.data_ptr() if recv_exps is not None else None
     b.count = len(pkt_ids)
@@ -601,21 +609,23 @@ def packet_burst(x, out, packet_numel: int, num_workers: int, batch_num_ltus: in
 
 
 def preprocess_burst(burst: PacketBurst, stream=None, like=None):
-    """sml_preprocess_burst: PreprocessSingle for every packet of the burst."""
-    _check("sml_preprocess_burst", lib().sml_preprocess_burst(ctypes.byref(burst), _stream(stream, like)))
+    """sml_preprocess_burst_typed: PreprocessSingle for every packet of the
+    burst (a FLOAT32 / INT32 burst is sml_preprocess_burst's)."""
+    _check("sml_preprocess_burst", lib().sml_preprocess_burst_typed(ctypes.byref(burst), _stream(stream, like)))
 
 
 def postprocess_burst(burst: PacketBurst, stream=None, like=None):
-    """sml_postprocess_burst: PostprocessSingle for every packet of the burst."""
-    _check("sml_postprocess_burst", lib().sml_postprocess_burst(ctypes.byref(burst), _stream(stream, like)))
+    """sml_postprocess_burst_typed: PostprocessSingle for every packet of the
+    burst (a FLOAT32 / INT32 burst is sml_postprocess_burst's)."""
+    _check("sml_postprocess_burst", lib().sml_postprocess_burst_typed(ctypes.byref(burst), _stream(stream, like)))
 
 
 def exchange_burst(burst: PacketBurst, stream=None, like=None):
-    """sml_exchange_burst: for every received packet q, PostprocessSingle(q)
+    """sml_exchange_burst_typed: for every received packet q, PostprocessSingle(q)
     then PreprocessSingle(q + b) into the same buffer (the DPDK receive loop's
     post + ReusePacket) in one launch; FLAG_PROCESS_PACKET applies the dummy
     backend's ProcessPacket (x W) first."""
-    _check("sml_exchange_burst", lib().sml_exchange_burst(ctypes.byref(burst), _stream(stream, like)))
+    _check("sml_exchange_burst", lib().sml_exchange_burst_typed(ctypes.byref(burst), _stream(stream, like)))
 
 
 BURST_PRE, BURST_POST, BURST_EXCHANGE = 0, 1, 2

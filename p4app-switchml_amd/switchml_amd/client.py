@@ -67,8 +67,8 @@ def make_config(**kw) -> str:
         "backend", "scheduler", "prepostprocessor", "instant_job_completion")}
     dummy = {k: v for k, v in kw.items() if k in ("bandwidth", "process_packets", "fail_worker_thread",
                                                   "stall_worker_thread", "stall_ms")}
-    hip = {k: v for k, v in kw.items() if k in ("device", "mode", "packet_ring", "burst_server", "batch_jobs",
-                                                     "coalesce_us", "vcl")}
+    hip = {k: v for k, v in kw.items() if k in ("device", "mode", "packet_ring", "burst_server", "half_packets",
+                                                     "batch_jobs", "coalesce_us", "vcl")}
     xgmi = {k: v for k, v in kw.items() if k in ("session", "max_slice_numel", "timeout_ms", "push", "half_types",
                                                   "fail_setup")}
     unknown = set(kw) - set(general) - set(dummy) - set(hip) - set(xgmi)
