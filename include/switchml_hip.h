@@ -275,13 +275,21 @@ sml_status_t sml_roundtrip_loopback_batch_typed(const sml_typed_slice* slices, u
 
 /* The switch's exponent half alone (p4/exponents.p4:48-54): d_exps_out[k] =
  * max_w (int8) d_exps[w][k], k < num_blocks — W planes of num_blocks bytes
- * (local or mapped peers' planes; HOST array of DEVICE pointers). */
+ * (local or mapped peers' planes; HOST array of DEVICE pointers).  Planes
+ * and output at any byte alignment (one dword per plane and 4 blocks when all
+ * are 4-byte aligned, bytes otherwise).
+ * Status, in this order: num_workers == 0, d_exps NULL or d_exps_out NULL ->
+ * SML_ERR_INVALID_ARG; num_workers > SML_MAX_SWITCH_WORKERS ->
+ * SML_ERR_UNSUPPORTED; num_blocks == 0 -> SML_OK (nothing to do, the table is
+ * not read); a NULL plane in the table -> SML_ERR_INVALID_ARG. */
 sml_status_t sml_switch_exps(const int8_t* const* d_exps, uint16_t num_workers, uint64_t num_blocks,
                              int8_t* d_exps_out, uint32_t flags, void* stream);
 
 /* Copy num_words 32-bit words (any 4-byte alignment; either side may be a
  * peer's mapped plane or pinned host memory): the all-gather step of the
- * in-node switch backend.  16-B accesses, the streaming kernels' tile shape. */
+ * in-node switch backend.  16-B accesses, the streaming kernels' tile shape.
+ * Status: num_words == 0 -> SML_OK whatever the pointers; else a NULL
+ * pointer or one not 4-byte aligned, on either side -> SML_ERR_INVALID_ARG. */
 sml_status_t sml_copy_words(const void* d_src, void* d_dst, uint64_t num_words, void* stream);
 
 /* Up to SML_MAX_SWITCH_WORKERS copies in ONE launch: d_dsts[i][0..n_i) =
@@ -594,7 +602,12 @@ sml_status_t sml_rx_reset(uint64_t* d_state, uint64_t num_words, void* stream);
 /* ncclUint8 buckets of the CollNet plugin (switchml_plugin.cc:318-337,
  * 370-378: "SwitchML does not really support uint8"): each byte widened to an
  * int32 for the INT32 all-reduce, and the summed words narrowed back (mod
- * 256).  Device or device-mapped memory; one launch each on `stream`. */
+ * 256).  Device or device-mapped memory; one launch each on `stream`.
+ * Widening zero-extends (a byte is 0..255); narrowing keeps the low byte.
+ * The uint8 side may start at any byte; the int32 side is 4-byte aligned.
+ * Status (both): n == 0 -> SML_OK whatever the pointers; else a NULL pointer,
+ * or an int32 side (sml_widen_u8_i32's d_out, sml_narrow_i32_u8's d_in) not
+ * 4-byte aligned -> SML_ERR_INVALID_ARG. */
 sml_status_t sml_widen_u8_i32(const uint8_t* d_in, int32_t* d_out, uint64_t n, void* stream);
 sml_status_t sml_narrow_i32_u8(const int32_t* d_in, uint8_t* d_out, uint64_t n, void* stream);
 

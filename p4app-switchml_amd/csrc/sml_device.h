@@ -262,11 +262,23 @@ __device__ __forceinline__ float widen16(uint16_t h) {
 // Round to nearest even; overflow -> +-inf, fp16 results below the normal
 // range -> fp16 denormals (the units are built without denormal flushing),
 // NaN -> a NaN of the type: v_cvt_f16_f32 / v_cvt_pk_bf16_f32.
+//
+// The fp16 conversion must round the fp32 value it is handed.  Left visible
+// to instruction selection, an fp32 multiply that feeds it (the reciprocal
+// form's q * (1 / s), dequant1<true>) is fused with it into
+// v_fma_mixlo_f16 a, b, 0, and the +0 addend turns a product of -0 (q < 0
+// under a scale of +inf, exponent -128) into +0 where PostprocessSingle's
+// division gives -0.  The empty asm makes f an opaque VGPR value; it holds no
+// instruction, so there is nothing in it for the hazard recognizer to miss.
 template <int H>
 __device__ __forceinline__ uint16_t narrow16(float f) {
     static_assert(H == kHalfF16 || H == kHalfBF16, "fp16 or bf16");
-    if constexpr (H == kHalfF16) return __builtin_bit_cast(uint16_t, (_Float16)f);
-    else return __builtin_bit_cast(uint16_t, (__bf16)f);
+    if constexpr (H == kHalfF16) {
+        asm("" : "+v"(f));
+        return __builtin_bit_cast(uint16_t, (_Float16)f);
+    } else {
+        return __builtin_bit_cast(uint16_t, (__bf16)f);
+    }
 }
 
 // Four 16-bit elements = one 8-byte access per lane.  Slices start at any

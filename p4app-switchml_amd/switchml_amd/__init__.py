@@ -534,6 +534,67 @@ def switch_aggregate(payloads, exps=None, numel: int | None = None, packet_numel
     return out
 
 
+def switch_exps(exps, out=None, flags: int = 0, stream=None):
+    """sml_switch_exps: the switch's exponent half alone, out[k] = the signed
+    int8 max over the W planes `exps` (int8, equal length) of byte k
+    (p4/exponents.p4:48-54).  The planes and `out` may sit at any byte
+    alignment.  flags = FLAG_PEER_PLANES when planes were written by other
+    GPUs.  Returns `out`."""
+    torch = _torch()
+    W = len(exps)
+    if W == 0 or W > MAX_SWITCH_WORKERS:
+        raise ValueError(f"1 <= workers <= {MAX_SWITCH_WORKERS}, got {W}")
+    B = exps[0].numel()
+    if any(e.numel() != B for e in exps):
+        raise ValueError("exponent planes differ in size")
+    if out is None:
+        out = torch.empty(B, dtype=torch.int8, device=exps[0].device)
+    elif out.numel() != B:
+        raise ValueError(f"out must hold B = {B} bytes")
+    ep = (ctypes.c_void_p * W)(*[_dev(e, torch.int8, "exps[w]").value for e in exps])
+    _check("sml_switch_exps", lib().sml_switch_exps(
+        ctypes.cast(ep, ctypes.c_void_p), W, B, _dev(out, torch.int8, "out"), flags, _stream(stream, exps[0])))
+    return out
+
+
+def copy_words(src, dst, stream=None):
+    """sml_copy_words: `src` copied into `dst`, 32-bit tensors of equal numel
+    (any 32-bit dtypes, any 4-byte alignment; CUDA or pinned host).  Returns
+    `dst`."""
+    if src.numel() != dst.numel() or src.element_size() != 4 or dst.element_size() != 4:
+        raise ValueError("src and dst are 32-bit tensors of equal numel")
+    _check("sml_copy_words", lib().sml_copy_words(_dev(src, src.dtype, "src"), _dev(dst, dst.dtype, "dst"),
+                                                  src.numel(), _stream(stream, src)))
+    return dst
+
+
+def widen_u8_i32(x, out=None, stream=None):
+    """sml_widen_u8_i32: each uint8 of `x` zero-extended into an int32 (the
+    CollNet plugin's ncclUint8 buckets on their way into the INT32
+    all-reduce).  `x` may start at any byte.  Returns `out`."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(x.numel(), dtype=torch.int32, device=x.device)
+    elif out.numel() != x.numel():
+        raise ValueError("x and out differ in numel")
+    _check("sml_widen_u8_i32", lib().sml_widen_u8_i32(_dev(x, torch.uint8, "x"), _dev(out, torch.int32, "out"),
+                                                      x.numel(), _stream(stream, x)))
+    return out
+
+
+def narrow_i32_u8(x, out=None, stream=None):
+    """sml_narrow_i32_u8: the low byte of each int32 of `x` (the sum mod 256),
+    back into a uint8 bucket at any byte.  Returns `out`."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(x.numel(), dtype=torch.uint8, device=x.device)
+    elif out.numel() != x.numel():
+        raise ValueError("x and out differ in numel")
+    _check("sml_narrow_i32_u8", lib().sml_narrow_i32_u8(_dev(x, torch.int32, "x"), _dev(out, torch.uint8, "out"),
+                                                        x.numel(), _stream(stream, x)))
+    return out
+
+
 def _segment_tables(pairs, dtype=None):
     """The three tables of a segment copy — sources, destinations, element
     counts, as void* — from (src, dst) tensor pairs of equal numel, all of

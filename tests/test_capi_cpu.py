@@ -204,6 +204,71 @@ def test_burst_server_validation_without_gpu(sw):
     assert L.sml_burst_server_destroy(None) == sw.SML_OK
 
 
+def test_switch_exps_validation_without_gpu(sw):
+    """sml_switch_exps refuses bad arguments before any launch, in the order
+    include/switchml_hip.h states: no workers / no table / no output, too
+    many workers, nothing to do, a NULL plane inside the table."""
+    L = sw.lib()
+    vp = ctypes.c_void_p
+    f = L.sml_switch_exps
+    bad = sw.SML_ERR_INVALID_ARG
+    table = (vp * 17)(*[16 + 4 * w for w in range(17)])
+    tab = ctypes.cast(table, vp)
+    out = vp(4096)
+    assert f(tab, 0, 8, out, 0, None) == bad                       # W = 0
+    assert f(None, 1, 8, out, 0, None) == bad                      # no table
+    assert f(tab, 1, 8, None, 0, None) == bad                      # no output
+    assert f(None, 0, 0, None, 0, None) == bad                     # ... even with nothing to do
+    assert f(tab, 17, 8, out, 0, None) == sw.SML_ERR_UNSUPPORTED   # > SML_MAX_SWITCH_WORKERS
+    assert f(tab, 17, 0, out, 0, None) == sw.SML_ERR_UNSUPPORTED   # the worker count is looked at first
+    assert f(tab, 16, 0, out, 0, None) == sw.SML_OK                # num_blocks = 0
+    assert f(tab, 16, 0, out, sw.FLAG_PEER_PLANES, None) == sw.SML_OK
+    for hole in (0, 2, 15):
+        holed = (vp * 16)(*[None if w == hole else 16 + 4 * w for w in range(16)])
+        assert f(ctypes.cast(holed, vp), 16, 8, out, 0, None) == bad, hole
+        assert f(ctypes.cast(holed, vp), 16, 0, out, 0, None) == sw.SML_OK   # the table is not read
+
+
+def test_copy_words_validation_without_gpu(sw):
+    """sml_copy_words: no words is nothing to do; a NULL or a pointer off its
+    4-byte alignment, on either side, is an invalid argument."""
+    L = sw.lib()
+    vp = ctypes.c_void_p
+    f = L.sml_copy_words
+    bad = sw.SML_ERR_INVALID_ARG
+    assert f(None, None, 0, None) == sw.SML_OK
+    assert f(vp(17), vp(18), 0, None) == sw.SML_OK
+    assert f(None, vp(32), 4, None) == bad
+    assert f(vp(16), None, 4, None) == bad
+    for off in (1, 2, 3):
+        assert f(vp(16 + off), vp(32), 4, None) == bad, off
+        assert f(vp(16), vp(32 + off), 4, None) == bad, off
+
+
+def test_widen_narrow_u8_validation_without_gpu(sw):
+    """sml_widen_u8_i32 / sml_narrow_i32_u8: n = 0 is nothing to do; a NULL on
+    either side or an int32 side off its 4-byte alignment is an invalid
+    argument.  (The uint8 side may start at any byte: such a call launches, so
+    it is not made here.)"""
+    L = sw.lib()
+    vp = ctypes.c_void_p
+    bad = sw.SML_ERR_INVALID_ARG
+    widen, narrow = L.sml_widen_u8_i32, L.sml_narrow_i32_u8
+    assert widen(None, None, 0, None) == sw.SML_OK
+    assert widen(vp(17), vp(18), 0, None) == sw.SML_OK
+    assert widen(None, vp(32), 4, None) == bad
+    assert widen(vp(16), None, 4, None) == bad
+    assert narrow(None, None, 0, None) == sw.SML_OK
+    assert narrow(vp(18), vp(17), 0, None) == sw.SML_OK
+    assert narrow(None, vp(32), 4, None) == bad
+    assert narrow(vp(16), None, 4, None) == bad
+    for off in (1, 2, 3):
+        assert widen(vp(16), vp(32 + off), 4, None) == bad, off     # int32 output
+        assert widen(vp(16 + off), vp(32 + off), 4, None) == bad, off
+        assert narrow(vp(32 + off), vp(16), 4, None) == bad, off    # int32 input
+        assert narrow(vp(32 + off), vp(16 + off), 4, None) == bad, off
+
+
 def test_grid_limit_knob(sw):
     prev = sw.set_grid_limit(1024)
     assert sw.set_grid_limit(prev) == 1024

@@ -251,6 +251,22 @@ def test_k4h_fp16_lands_in_denormal_range(cuda, P):
     assert ((b & 0x7C00) == 0).all() and ((b & 0x03FF) != 0).mean() > 0.9   # denormals, not flushed to zero
 
 
+@pytest.mark.parametrize("W", (1, 2, 3))
+@pytest.mark.parametrize("P", PS)
+@pytest.mark.parametrize("T", TYPES)
+def test_k4h_keeps_the_sign_of_zero(cuda, T, P, W):
+    """Exponent -128: the scale is +inf, so every output is a zero with the
+    sign of its word (q / inf), through the division (W = 3) and through the
+    exact reciprocal (W = 1, 2: q * 0), whose fp32 multiply must not be fused
+    into the fp16 conversion (an fma with a +0 addend gives +0 for -0)."""
+    rng = np.random.default_rng(8)
+    q = rng.integers(-2 ** 31, 2 ** 31, size=4113, dtype=np.int64).astype(np.int32)
+    q[:8] = (-1, 1, 0, -2 ** 31, -1, -1, -1, -1)
+    y32, got = k4h_case(cuda, T, q, -128, P, W)
+    assert (y32 == 0).all() and np.array_equal(np.signbit(y32), q < 0)
+    assert np.array_equal(bits_of(got), np.where(q < 0, 0x8000, 0).astype(np.uint16))
+
+
 @pytest.mark.parametrize("P", PS)
 def test_k4h_bf16_exact_rne_ties(cuda, P):
     i = np.arange(4113)
