@@ -599,6 +599,97 @@ sml_status_t sml_unpack_frames_int32(const void* frames, uint64_t num_frames, ui
  * call.  One async memset on `stream`. */
 sml_status_t sml_rx_reset(uint64_t* d_state, uint64_t num_words, void* stream);
 
+/* ---- The switch's side of the DPDK frames (SURVEY §8 A11 over F3) --------
+ * What the Tofino pipeline does to the frames W workers send it, a batch of
+ * arrived frames per call, with the switch's registers in d_state across
+ * calls: the slot pool with its two sets, the worker bitmap and the worker
+ * count (p4/bitmap_checker.p4, p4/workers_counter.p4), the wrapping bit<32>
+ * sum and the signed int8 exponent max (p4/processor.p4:48-54,
+ * p4/exponents.p4:48-54), the "last packet broadcasts, a retransmission to a
+ * full slot is answered, anything else is consumed" rule
+ * (p4/next_step_selector.p4, controller/next_step_selector.py) and the result
+ * frame (p4/udp_sender.p4).
+ *   A frame is one of sml_quantize_pack_frames' / sml_pack_frames_int32's.  Its
+ * worker w is the index of workers[] whose ip_be equals bytes 26-29, its slot
+ * s the 14 low bits of the big-endian pool index at bytes 48-49, its set v
+ * that index's bit 15.  An unknown source address or s >= num_slots: IGNORED,
+ * nothing changes.  Otherwise, frame by frame in index order:
+ *   before = bitmap[s][v]; bitmap[s][v] |= 1 << w; bitmap[s][1-v] &= ~(1 << w);
+ *   not a retransmission (before has no bit w): flag = count[s][v], then
+ *     count = count == 0 ? W - 1 : count - 1 (W == 1: flag = 1); the slot's P
+ *     words and two exponent bytes are WRITTEN when before == 0, else the words
+ *     are added mod 2^32 (host order; the result carries htonl) and the
+ *     exponents take the signed int8 max, byte 50 and byte 51 each on its own;
+ *     flag == 1 -> BROADCAST, else CONSUMED;
+ *   a retransmission: flag = count[s][v], unchanged (W == 1: flag = 0);
+ *     flag == 0, a full slot -> RETRANSMIT, else CONSUMED.
+ * BROADCAST / RETRANSMIT: the result frame is written at out_frames +
+ * i * out_stride for input frame i (every other output position keeps its
+ * bytes).  Eth dst = workers[w].mac, src = switch_mac, IPv4 (0x45 0x00, total
+ * length, id / flags / fragment 0, TTL 64, UDP, a real header checksum, src =
+ * the switch, dst = the worker), UDP (src port = the frame's dst port, dst
+ * port = its src port, length, checksum 0), byte 42 = 0x10 | (byte 42 & 7),
+ * bytes 43-47 echoed, bytes 48-49 the received pool index with bit 14 cleared,
+ * bytes 50-51 the slot's exponents, from byte 52 the slot's P words.  A
+ * BROADCAST is written once, addressed to the worker whose frame completed
+ * the slot: the other W - 1 copies differ in the destination fields and the
+ * checksum only and are the caller's to make.
+ *   One call is that pipeline over the call's frames in index order, with one
+ * rule that makes it parallel: for each (slot, worker) the call handles the
+ * frames of the set that pair's lowest-index frame carries; the pair's frames
+ * of the other set get DEFERRED and change nothing — the caller resubmits
+ * them in a later call, a reordering the network could have produced.  Equal
+ * to the sequential pipeline for streams that follow the worker protocol (a
+ * worker sends packet p + max_outstanding into a slot only after it received
+ * the result of packet p from it; loss, duplication and reordering within
+ * that window).  For any other stream the verdicts, the bitmaps and the counts
+ * are still the pipeline's, and a result frame carries the slot's words as
+ * they stand at the END of the call (an answer to a retransmission that
+ * precedes a new contribution to its slot and set in the same call differs).
+ *   frames / out_frames: device memory or pinned, device-mapped host memory,
+ *     4-byte aligned, strides >= sml_frame_bytes(P) and a multiple of 4;
+ *   d_state: sml_frame_switch_state_bytes() bytes of device memory, 8-byte
+ *     aligned, opaque, cleared by sml_frame_switch_reset before the first call;
+ *   d_verdict: uint8[num_frames], out;  d_counts: uint64[5] indexed by
+ *     verdict, added to; nullable, 8-byte aligned.
+ * Status, every check before any launch: params NULL, num_workers == 0, or
+ * (num_frames > 0) a NULL frames / d_state / out_frames / d_verdict ->
+ * SML_ERR_INVALID_ARG; packet_numel not a packet size, num_workers >
+ * SML_MAX_FRAME_SWITCH_WORKERS, num_slots not in 1..16384 ->
+ * SML_ERR_UNSUPPORTED; num_frames == 0 -> SML_OK, nothing launched; a buffer
+ * or stride off its alignment -> SML_ERR_ALIGNMENT.
+ * Four launches on `stream`: claim (thread per frame), verdicts (thread per
+ * frame), apply (wave per touched slot), results (wave per input frame; it
+ * writes only for a BROADCAST / RETRANSMIT verdict). */
+#define SML_MAX_FRAME_SWITCH_WORKERS 32          /* worker_bitmap_t is 32 bits */
+#define SML_MAX_FRAME_SWITCH_SLOTS 16384         /* pool indices 0..16383, two sets each */
+#define SML_VERDICT_CONSUMED   0
+#define SML_VERDICT_BROADCAST  1
+#define SML_VERDICT_RETRANSMIT 2
+#define SML_VERDICT_IGNORED    3
+#define SML_VERDICT_DEFERRED   4
+typedef struct sml_switch_worker { uint8_t mac[6]; uint32_t ip_be; } sml_switch_worker;
+typedef struct sml_frame_switch_params {
+    uint8_t  switch_mac[6];  uint32_t switch_ip_be;
+    uint16_t num_workers;                    /* 1..32 */
+    uint32_t num_slots;                      /* 1..16384: pool indices 0..num_slots-1, two sets each */
+    uint32_t packet_numel;                   /* 64,128,256,512,1024 */
+    sml_switch_worker workers[SML_MAX_FRAME_SWITCH_WORKERS];
+} sml_frame_switch_params;
+
+/* Bytes of d_state for a pool of num_slots slots of packet_numel words; 0 on
+ * an unsupported packet_numel or num_slots. */
+uint64_t sml_frame_switch_state_bytes(uint32_t num_slots, uint32_t packet_numel);
+/* Clear the switch's registers (bitmaps, counts, the per-call scratch): async
+ * memsets on `stream`.  Status: d_state NULL -> SML_ERR_INVALID_ARG; bad
+ * num_slots / packet_numel -> SML_ERR_UNSUPPORTED; d_state not 8-byte aligned
+ * -> SML_ERR_ALIGNMENT. */
+sml_status_t sml_frame_switch_reset(void* d_state, uint32_t num_slots, uint32_t packet_numel, void* stream);
+sml_status_t sml_frame_switch(const sml_frame_switch_params* params,
+                              const void* frames, uint64_t num_frames, uint64_t frame_stride,
+                              void* d_state, void* out_frames, uint64_t out_stride,
+                              uint8_t* d_verdict, uint64_t* d_counts, void* stream);
+
 /* ncclUint8 buckets of the CollNet plugin (switchml_plugin.cc:318-337,
  * 370-378: "SwitchML does not really support uint8"): each byte widened to an
  * int32 for the INT32 all-reduce, and the summed words narrowed back (mod

@@ -1,0 +1,447 @@
+// sml_switch_frames.hip — the switch's side of the DPDK frames on gfx950
+// ("Switch side"): the Tofino pipeline's slot logic
+// (p4/bitmap_checker.p4, p4/workers_counter.p4, p4/next_step_selector.p4,
+// p4/udp_sender.p4) with the aggregation pinned on planes by K6
+// (p4/processor.p4:48-54, p4/exponents.p4:48-54), over a batch of arrived
+// frames per call and registers that persist in d_state.
+//
+// The pipeline is sequential per slot; a call makes it parallel with the
+// claim-then-apply shape of the receive side (sml_frames.hip):
+//   k_fs_claim    thread per frame: a 64-bit atomic on the (slot, worker) word
+//                 keeps the pair's lowest-index frame and its set — the set the
+//                 call handles for the pair (the other set's frames: DEFERRED).
+//   k_fs_verdict  thread per frame: with the slot's <= 32 claim words and the
+//                 registers as the call found them, a frame knows the whole
+//                 history of its slot up to its own index — who contributed
+//                 before it — hence its flag and its verdict.  The frame that
+//                 is its slot's first lists the slot as touched.
+//   k_fs_apply    wave per touched slot: the new contributors' payloads summed
+//                 into (or written over) the slot's words, the exponents maxed,
+//                 bitmap and count advanced, the claim words cleared.
+//   k_fs_result   wave per input frame: it loads the frame's header dwords and
+//                 its verdict, and on BROADCAST / RETRANSMIT writes
+//                 udp_sender's frame from the slot's words (any other verdict:
+//                 the wave ends there).
+// Each launch reads only what an earlier launch on the stream (or an earlier
+// call) wrote and no workgroup waits on another: within a launch every claim
+// word, register and accumulator word has one writer (the wave of its slot)
+// or is only read.
+//
+// d_state: [0] the touched-slot count; claim words uint64[S][32] (0 = none,
+// else ~((frame << 1) | set), so atomicMax keeps the lowest frame); per
+// (slot, set) bitmap, count and exponent pair (uint32 each); the touched list
+// uint32[S]; the accumulators uint32[S][2][P] in host order.
+#include "sml_host.h"
+
+namespace sml {
+
+constexpr uint32_t kFsMaxWorkers = SML_MAX_FRAME_SWITCH_WORKERS;
+constexpr uint64_t kFsHead = 64;                   // bytes before the claim words
+
+struct FsWorker {
+    uint32_t mac_lo;        // mac[0..3], memory order
+    uint32_t mac_hi_ck;     // mac[4..5] | IPv4 header checksum of a result to this worker (bytes 24-25) << 16
+    uint32_t ip;            // ip_be, memory order
+};
+
+struct FsArgs {
+    const uint8_t* frames;
+    uint64_t nframes;
+    uint64_t stride;
+    uint8_t* out;
+    uint64_t out_stride;
+    uint8_t* verdict;
+    unsigned long long* counts;     // [5] or nullptr
+    uint32_t* touched_count;
+    unsigned long long* claims;     // [S][32]
+    uint32_t* bitmap;               // [S][2]
+    uint32_t* count;                // [S][2]
+    uint32_t* exps;                 // [S][2]: byte 50 | byte 51 << 8
+    uint32_t* touched;              // [S]
+    uint32_t* acc;                  // [S][2][P]
+    uint32_t S, W;
+    uint32_t sw_mac_lo16;           // switch mac[0..1]
+    uint32_t sw_mac_hi;             // switch mac[2..5]
+    uint32_t sw_ip;
+    uint32_t len_dw4;               // result bytes 16-19: IPv4 total length (BE), identification 0
+    uint32_t udp_len_be;            // result bytes 38-39 as a 16-bit value in memory order
+    FsWorker workers[kFsMaxWorkers];
+};
+
+// What the parser and the worker table make of frame f.
+struct FsHdr {
+    uint32_t w, s, v;
+    bool ok;                        // a known worker and a slot of the pool
+};
+
+__device__ __forceinline__ FsHdr fs_header(const FsArgs& a, uint32_t d6, uint32_t d7, uint32_t d12) {
+    const uint32_t ip = (d6 >> 16) | (d7 << 16);               // bytes 26-29
+    const uint32_t idx = ((d12 & 0xffu) << 8) | ((d12 >> 8) & 0xffu);   // bytes 48-49, big-endian
+    FsHdr h;
+    h.w = kFsMaxWorkers;
+    for (uint32_t u = 0; u < a.W; u++) h.w = (a.workers[u].ip == ip && h.w == kFsMaxWorkers) ? u : h.w;
+    h.s = idx & 0x3fffu;
+    h.v = idx >> 15;
+    h.ok = h.w < kFsMaxWorkers && h.s < a.S;
+    return h;
+}
+
+__device__ __forceinline__ FsHdr fs_header(const FsArgs& a, uint64_t f) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(a.frames + f * a.stride);
+    const uint32_t d6 = p[6], d7 = p[7], d12 = p[12];
+    return fs_header(a, d6, d7, d12);
+}
+
+// workers_counter.p4's register action, n times: 0 -> W - 1, else one down.
+__device__ __forceinline__ uint32_t fs_count_after(uint32_t c, uint32_t n, uint32_t W) {
+    for (uint32_t i = 0; i < n; i++) c = c == 0 ? W - 1 : c - 1;
+    return c;
+}
+
+__device__ __forceinline__ unsigned long long fs_claim_word(uint64_t f, uint32_t v) {
+    return ~(((unsigned long long)f << 1) | v);
+}
+
+// Pass 1: the (slot, worker) pair's lowest-index frame, with its set.
+__global__ __launch_bounds__(kBlockThreads) void k_fs_claim(FsArgs a) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.touched_count = 0;      // this call's list starts empty
+    const uint64_t stride = (uint64_t)gridDim.x * kBlockThreads;
+    for (uint64_t f = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x; f < a.nframes; f += stride) {
+        const FsHdr h = fs_header(a, f);
+        if (h.ok) atomicMax(a.claims + (uint64_t)h.s * kFsMaxWorkers + h.w, fs_claim_word(f, h.v));
+    }
+}
+
+// Pass 2: every frame's verdict from the registers as the call found them and
+// its slot's claim words.  In the call, worker u touches slot s once as far as
+// the registers go — at its claimed frame f_u, in its call set: there bit u of
+// that set's bitmap is set and bit u of the other set's cleared, and if the
+// bit was clear, u is a new contributor: the count steps.  Every later frame
+// of u (same set) finds its bit set: a retransmission.  So the count that
+// frame f sees is the call's starting count stepped once per new contributor
+// of its set claimed below f.
+__global__ __launch_bounds__(kBlockThreads) void k_fs_verdict(FsArgs a) {
+    __shared__ uint32_t hist[5];
+    if (threadIdx.x < 5) hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * kBlockThreads;
+    for (uint64_t f = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x; f < a.nframes; f += stride) {
+        const FsHdr h = fs_header(a, f);
+        uint32_t verdict = SML_VERDICT_IGNORED;
+        bool lists = false;
+        if (h.ok) {
+            const unsigned long long* cl = a.claims + (uint64_t)h.s * kFsMaxWorkers;
+            const unsigned long long mine = ~cl[h.w];
+            const uint32_t bm = a.bitmap[2 * h.s + h.v];
+            const uint32_t c0 = a.count[2 * h.s + h.v];
+            if ((uint32_t)(mine & 1ull) != h.v) {
+                verdict = SML_VERDICT_DEFERRED;
+            } else {
+                uint32_t nbefore = 0;                  // new contributors of (s, v) claimed below f
+                uint64_t first = ~0ull;                // the slot's lowest claimed frame
+                for (uint32_t u = 0; u < a.W; u++) {
+                    const unsigned long long c = cl[u];
+                    if (c == 0ull) continue;
+                    const uint64_t fu = (~c) >> 1;
+                    first = fu < first ? fu : first;
+                    if ((uint32_t)((~c) & 1ull) == h.v && !((bm >> u) & 1u) && fu < f) nbefore++;
+                }
+                const bool fresh = (mine >> 1) == f && !((bm >> h.w) & 1u);
+                uint32_t flag = fs_count_after(c0, nbefore, a.W);
+                if (a.W == 1) flag = fresh ? 1u : 0u;
+                if (fresh) verdict = flag == 1u ? SML_VERDICT_BROADCAST : SML_VERDICT_CONSUMED;
+                else verdict = flag == 0u ? SML_VERDICT_RETRANSMIT : SML_VERDICT_CONSUMED;
+                lists = first == f;                    // once per touched slot
+            }
+            // a deferred frame can be its slot's first only if it is its pair's
+            // first, and then it is not deferred: the list is complete
+        }
+        a.verdict[f] = (uint8_t)verdict;
+        if (lists) a.touched[atomicAdd(a.touched_count, 1u)] = h.s;
+        if (a.counts) atomicAdd(&hist[verdict], 1u);
+    }
+    if (!a.counts) return;
+    __syncthreads();
+    if (threadIdx.x < 5 && hist[threadIdx.x]) atomicAdd(a.counts + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
+}
+
+__device__ __forceinline__ int fs_max_i8(uint32_t a, uint32_t b) {
+    const int x = (int8_t)a, y = (int8_t)b;
+    return x > y ? x : y;
+}
+
+// Pass 3, wave per touched slot: lane u < W holds worker u's claim.  Per set:
+// the bitmap's bits move as the claims say; the new contributors (claimed in
+// this set, bit clear at the start) are summed in.  A contributor that found
+// the bitmap empty at its index WRITES (p4/processor.p4:99-102): whatever the
+// slot held, and whatever was added below that index, is gone — the sum starts
+// at the last such contributor (the first, for any stream that follows the
+// protocol).
+template <int P>
+__global__ __launch_bounds__(kBlockThreads) void k_fs_apply(FsArgs a) {
+    constexpr int kChunks = P / 4;                             // 16-byte chunks of a payload
+    constexpr int kPer = (kChunks + kWave - 1) / kWave;        // chunks per lane
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t nwaves = gridDim.x * kWavesPerBlock;
+    const uint32_t ntouched = *a.touched_count;
+    for (uint32_t i = blockIdx.x * kWavesPerBlock + wave_index(); i < ntouched; i += nwaves) {
+        const uint32_t s = a.touched[i];
+        unsigned long long* const clp = a.claims + (uint64_t)s * kFsMaxWorkers;
+        const unsigned long long c = lane < (int)kFsMaxWorkers ? clp[lane] : 0ull;
+        const uint64_t fu = (~c) >> 1;
+        const bool live = c != 0ull && fu < a.nframes;         // (a claim names a frame of this call)
+        const uint32_t cs = (uint32_t)((~c) & 1ull);
+        // exponent bytes of this lane's claimed frame (bytes 50-51)
+        uint32_t ed = 0;
+        if (live) ed = *reinterpret_cast<const uint32_t*>(a.frames + fu * a.stride + 48) >> 16;
+#pragma unroll 1
+        for (uint32_t v = 0; v < 2; v++) {
+            const uint32_t setmask = (uint32_t)__ballot(live && cs == v);
+            const uint32_t clrmask = (uint32_t)__ballot(live && cs != v);
+            if (!(setmask | clrmask)) continue;
+            const uint32_t bm0 = a.bitmap[2 * s + v];
+            const uint32_t c0 = a.count[2 * s + v];
+            const bool contrib = live && cs == v && !((bm0 >> lane) & 1u);
+            const uint32_t cmask = (uint32_t)__ballot(contrib);
+            // the bitmap as this lane's claimed frame finds it
+            uint32_t before = bm0;
+            for (uint32_t x = 0; x < a.W; x++) {
+                const uint64_t fx = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(fu >> 32), (int)x) << 32) |
+                                    (uint32_t)__shfl((int)(uint32_t)fu, (int)x);
+                if (fx < fu) {
+                    if ((setmask >> x) & 1u) before |= 1u << x;
+                    if ((clrmask >> x) & 1u) before &= ~(1u << x);
+                }
+            }
+            const bool writer = contrib && before == 0u;
+            const uint32_t wmask = (uint32_t)__ballot(writer);
+            uint64_t fw = 0;                                   // the last writer's frame
+            for (uint32_t m = wmask; m; m &= m - 1) {
+                const int j = __builtin_ctz(m);
+                const uint64_t fj = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(fu >> 32), j) << 32) |
+                                    (uint32_t)__shfl((int)(uint32_t)fu, j);
+                fw = fj > fw ? fj : fw;
+            }
+            const bool eff = contrib && (wmask == 0u || fu >= fw);
+            const uint32_t emask = (uint32_t)__ballot(eff);
+            if (cmask) {
+                // the contributors one after another (every lane takes part in
+                // the shuffle that names the frame), a lane's chunks side by side
+                uint32_t* const acc = a.acc + ((uint64_t)2 * s + v) * P;
+                u4 sum[kPer];
+#pragma unroll
+                for (int k = 0; k < kPer; k++) {
+                    const int ch = k * kWave + lane;
+                    sum[k] = mku4(0u, 0u, 0u, 0u);
+                    if (wmask == 0u && ch < kChunks) sum[k] = *reinterpret_cast<const u4*>(acc + 4 * ch);
+                }
+                for (uint32_t m = emask; m; m &= m - 1) {
+                    const int j = __builtin_ctz(m);
+                    const uint64_t fj = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(fu >> 32), j) << 32) |
+                                        (uint32_t)__shfl((int)(uint32_t)fu, j);
+                    const uint8_t* const pl = a.frames + fj * a.stride + 52;
+                    u4a w[kPer];
+#pragma unroll
+                    for (int k = 0; k < kPer; k++) {
+                        const int ch = k * kWave + lane;
+                        // a lane past the payload (P < 256) rereads chunk 0 and drops it
+                        w[k] = __builtin_nontemporal_load(reinterpret_cast<const u4a*>(pl + 16 * (ch < kChunks ? ch : 0)));
+                    }
+#pragma unroll
+                    for (int k = 0; k < kPer; k++) {
+                        sum[k].x += bswap(w[k].x); sum[k].y += bswap(w[k].y);
+                        sum[k].z += bswap(w[k].z); sum[k].w += bswap(w[k].w);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < kPer; k++) {
+                    const int ch = k * kWave + lane;
+                    if (ch < kChunks) *reinterpret_cast<u4*>(acc + 4 * ch) = sum[k];
+                }
+                // exponents: signed int8 max, each byte on its own; -128 is the identity
+                int e0 = eff ? (int)(int8_t)(ed & 0xffu) : -128;
+                int e1 = eff ? (int)(int8_t)((ed >> 8) & 0xffu) : -128;
+#pragma unroll
+                for (int d = 1; d < (int)kFsMaxWorkers; d <<= 1) {
+                    const int o0 = __shfl_xor(e0, d), o1 = __shfl_xor(e1, d);
+                    e0 = o0 > e0 ? o0 : e0;
+                    e1 = o1 > e1 ? o1 : e1;
+                }
+                if (lane == 0) {
+                    if (wmask == 0u) {
+                        const uint32_t old = a.exps[2 * s + v];
+                        e0 = fs_max_i8(old & 0xffu, (uint32_t)e0 & 0xffu);
+                        e1 = fs_max_i8((old >> 8) & 0xffu, (uint32_t)e1 & 0xffu);
+                    }
+                    a.exps[2 * s + v] = ((uint32_t)e0 & 0xffu) | (((uint32_t)e1 & 0xffu) << 8);
+                }
+            }
+            if (lane == 0) {
+                a.bitmap[2 * s + v] = (bm0 | setmask) & ~clrmask;
+                a.count[2 * s + v] = fs_count_after(c0, (uint32_t)__builtin_popcount(cmask), a.W);
+            }
+        }
+        if (lane < (int)kFsMaxWorkers && c != 0ull) clp[lane] = 0ull;   // the next call's claims start empty
+    }
+}
+
+// Pass 4: udp_sender.p4's frame for every BROADCAST / RETRANSMIT verdict, a
+// wave per input frame (a wave whose frame has no result ends after its header
+// and verdict loads): lanes 0-12 store the 52 header bytes (a dword each),
+// every lane its 16-byte chunks of the slot's words, byte-swapped to wire
+// order.  One frame per wave keeps the result frames' load-to-store chains
+// (verdict, header, slot words) side by side instead of in series.
+template <int P>
+__global__ __launch_bounds__(kBlockThreads) void k_fs_result(FsArgs a) {
+    constexpr int kChunks = P / 4;
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
+    for (uint64_t f = (uint64_t)blockIdx.x * kWavesPerBlock + wave_index(); f < a.nframes; f += nwaves) {
+        // the header goes out with the verdict, not behind it
+        const uint32_t* in = reinterpret_cast<const uint32_t*>(a.frames + f * a.stride);
+        const uint32_t d6 = in[6], d7 = in[7], d8 = in[8], d9 = in[9], d10 = in[10], d11 = in[11], d12 = in[12];
+        const uint32_t vd = a.verdict[f];
+        if (vd != SML_VERDICT_BROADCAST && vd != SML_VERDICT_RETRANSMIT) continue;
+        const FsHdr h = fs_header(a, d6, d7, d12);
+        if (!h.ok) continue;                               // a verdict 1 / 2 is never an ignored frame's
+        const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.w);
+        const uint32_t sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(2 * h.s + h.v));
+        const FsWorker wk = a.workers[w];
+        const uint32_t ex = a.exps[sv];
+        uint32_t dw = wk.mac_lo;                                                        // bytes 0-3
+        dw = lane == 1 ? ((wk.mac_hi_ck & 0xffffu) | (a.sw_mac_lo16 << 16)) : dw;         // 4-7
+        dw = lane == 2 ? a.sw_mac_hi : dw;                                              // 8-11
+        dw = lane == 3 ? 0x00450008u : dw;                      // ethertype 0x0800, 0x45, 0x00
+        dw = lane == 4 ? a.len_dw4 : dw;                        // total length, identification 0
+        dw = lane == 5 ? 0x11400000u : dw;                      // flags / fragment 0, TTL 64, UDP
+        dw = lane == 6 ? ((wk.mac_hi_ck >> 16) | (a.sw_ip << 16)) : dw;                  // checksum, src ip
+        dw = lane == 7 ? ((a.sw_ip >> 16) | (wk.ip << 16)) : dw;                         // src ip, dst ip
+        dw = lane == 8 ? ((wk.ip >> 16) | (d9 << 16)) : dw;     // dst ip, src port = the frame's dst port
+        dw = lane == 9 ? ((d8 >> 16) | (a.udp_len_be << 16)) : dw;   // dst port = its src port, length
+        dw = lane == 10 ? (((0x10u | ((d10 >> 16) & 7u)) << 16) | (d10 & 0xff000000u)) : dw;   // cksum 0, type, job
+        dw = lane == 11 ? d11 : dw;                             // tsi
+        dw = lane == 12 ? ((d12 & 0xffbfu) | ((ex & 0xffffu) << 16)) : dw;   // pool index, bit 14 cleared; exponents
+        uint8_t* const o = a.out + f * a.out_stride;
+        if (lane < 13) reinterpret_cast<uint32_t*>(o)[lane] = dw;
+        const uint32_t* const acc = a.acc + (uint64_t)sv * P;
+        for (int ch = lane; ch < kChunks; ch += kWave) {
+            const u4 q = *reinterpret_cast<const u4*>(acc + 4 * ch);
+            *reinterpret_cast<u4a*>(o + 52 + 16 * ch) = u4a{bswap(q.x), bswap(q.y), bswap(q.z), bswap(q.w)};
+        }
+    }
+}
+
+// The pieces of d_state.
+struct FsLayout {
+    uint64_t claims, bitmap, count, exps, touched, acc, total;
+};
+
+static bool fs_layout(uint32_t S, uint32_t P, FsLayout& l) {
+    if (!valid_packet(P) || S == 0 || S > SML_MAX_FRAME_SWITCH_SLOTS) return false;
+    l.claims = kFsHead;
+    l.bitmap = l.claims + 8ull * kFsMaxWorkers * S;
+    l.count = l.bitmap + 8ull * S;
+    l.exps = l.count + 8ull * S;
+    l.touched = l.exps + 8ull * S;
+    l.acc = (l.touched + 4ull * S + 15) & ~15ull;
+    l.total = l.acc + 8ull * S * P;
+    return true;
+}
+
+// RFC 1071 over the 20 header bytes of a result to the worker at `ip`, as the
+// deparser fills it; returned as bytes 24-25 in memory order.
+static uint32_t fs_ipv4_checksum(uint32_t total_len, uint32_t src_ip, uint32_t dst_ip) {
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(&src_ip);
+    const uint8_t* d = reinterpret_cast<const uint8_t*>(&dst_ip);
+    uint32_t sum = 0x4500u + total_len + 0x4011u;
+    sum += ((uint32_t)s[0] << 8 | s[1]) + ((uint32_t)s[2] << 8 | s[3]);
+    sum += ((uint32_t)d[0] << 8 | d[1]) + ((uint32_t)d[2] << 8 | d[3]);
+    sum = (sum & 0xffffu) + (sum >> 16);
+    sum = (sum & 0xffffu) + (sum >> 16);
+    const uint32_t ck = ~sum & 0xffffu;
+    return (ck >> 8) | ((ck & 0xffu) << 8);
+}
+
+}  // namespace sml
+
+using namespace sml;
+
+extern "C" {
+
+uint64_t sml_frame_switch_state_bytes(uint32_t num_slots, uint32_t packet_numel) {
+    FsLayout l;
+    return fs_layout(num_slots, packet_numel, l) ? l.total : 0;
+}
+
+sml_status_t sml_frame_switch_reset(void* d_state, uint32_t num_slots, uint32_t packet_numel, void* stream) {
+    if (!d_state) return SML_ERR_INVALID_ARG;
+    FsLayout l;
+    if (!fs_layout(num_slots, packet_numel, l)) return SML_ERR_UNSUPPORTED;
+    if ((uintptr_t)d_state & 7u) return SML_ERR_ALIGNMENT;
+    // everything but the accumulators: a slot's words are written before they are read
+    return hip_check(hipMemsetAsync(d_state, 0, l.acc, (hipStream_t)stream));
+}
+
+sml_status_t sml_frame_switch(const sml_frame_switch_params* prm, const void* frames, uint64_t num_frames,
+                              uint64_t stride, void* d_state, void* out_frames, uint64_t out_stride,
+                              uint8_t* d_verdict, uint64_t* d_counts, void* stream) {
+    if (!prm || prm->num_workers == 0) return SML_ERR_INVALID_ARG;
+    if (num_frames && (!frames || !d_state || !out_frames || !d_verdict)) return SML_ERR_INVALID_ARG;
+    const uint32_t P = prm->packet_numel, S = prm->num_slots, W = prm->num_workers;
+    FsLayout l;
+    if (!fs_layout(S, P, l) || W > kFsMaxWorkers) return SML_ERR_UNSUPPORTED;
+    if (num_frames == 0) return SML_OK;
+    const uint64_t fb = sml_frame_bytes(P);
+    if (!aligned4(frames) || stride % 4 || stride < fb) return SML_ERR_ALIGNMENT;
+    if (!aligned4(out_frames) || out_stride % 4 || out_stride < fb) return SML_ERR_ALIGNMENT;
+    if (((uintptr_t)d_state & 7u) || (d_counts && ((uintptr_t)d_counts & 7u))) return SML_ERR_ALIGNMENT;
+
+    FsArgs a;
+    memset(&a, 0, sizeof(a));
+    uint8_t* const st8 = static_cast<uint8_t*>(d_state);
+    a.frames = static_cast<const uint8_t*>(frames);
+    a.nframes = num_frames;
+    a.stride = stride;
+    a.out = static_cast<uint8_t*>(out_frames);
+    a.out_stride = out_stride;
+    a.verdict = d_verdict;
+    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
+    a.touched_count = reinterpret_cast<uint32_t*>(st8);
+    a.claims = reinterpret_cast<unsigned long long*>(st8 + l.claims);
+    a.bitmap = reinterpret_cast<uint32_t*>(st8 + l.bitmap);
+    a.count = reinterpret_cast<uint32_t*>(st8 + l.count);
+    a.exps = reinterpret_cast<uint32_t*>(st8 + l.exps);
+    a.touched = reinterpret_cast<uint32_t*>(st8 + l.touched);
+    a.acc = reinterpret_cast<uint32_t*>(st8 + l.acc);
+    a.S = S;
+    a.W = W;
+    a.sw_mac_lo16 = (uint32_t)prm->switch_mac[0] | ((uint32_t)prm->switch_mac[1] << 8);
+    memcpy(&a.sw_mac_hi, prm->switch_mac + 2, 4);
+    a.sw_ip = prm->switch_ip_be;
+    const uint32_t total_len = (uint32_t)fb - 14, udp_len = (uint32_t)fb - 34;
+    a.len_dw4 = (total_len >> 8) | ((total_len & 0xffu) << 8);
+    a.udp_len_be = (udp_len >> 8) | ((udp_len & 0xffu) << 8);
+    for (uint32_t u = 0; u < W; u++) {
+        const sml_switch_worker& wk = prm->workers[u];
+        memcpy(&a.workers[u].mac_lo, wk.mac, 4);
+        a.workers[u].mac_hi_ck = (uint32_t)wk.mac[4] | ((uint32_t)wk.mac[5] << 8) |
+                                 (fs_ipv4_checksum(total_len, prm->switch_ip_be, wk.ip_be) << 16);
+        a.workers[u].ip = wk.ip_be;
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t gframes = grid_for_vec(num_frames);
+    k_fs_claim<<<gframes, kBlockThreads, 0, st>>>(a);
+    k_fs_verdict<<<gframes, kBlockThreads, 0, st>>>(a);
+    // at most one touched slot per frame, and per slot of the pool
+    const uint64_t slots = num_frames < S ? num_frames : S;
+    const uint32_t gslots = grid_for_tiles(slots);
+    const uint32_t gresult = grid_for_tiles(num_frames);
+    dispatch_packet(P, [&](auto Pc) {
+        k_fs_apply<Pc()><<<gslots, kBlockThreads, 0, st>>>(a);
+        k_fs_result<Pc()><<<gresult, kBlockThreads, 0, st>>>(a);
+    });
+    return launch_check();
+}
+
+}  // extern "C"

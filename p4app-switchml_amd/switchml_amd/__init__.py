@@ -64,6 +64,44 @@ def frame_params(dst_mac=b"\x02\x00\x00\x00\x00\x01", src_mac=b"\x02\x00\x00\x00
     return fp
 
 
+MAX_FRAME_SWITCH_WORKERS = 32
+MAX_FRAME_SWITCH_SLOTS = 16384
+# sml_frame_switch's verdict per input frame
+VERDICT_CONSUMED, VERDICT_BROADCAST, VERDICT_RETRANSMIT, VERDICT_IGNORED, VERDICT_DEFERRED = range(5)
+
+
+class SwitchWorker(ctypes.Structure):
+    """sml_switch_worker: a worker's MAC and its IPv4 address in network byte order."""
+    _fields_ = [("mac", ctypes.c_uint8 * 6), ("ip_be", ctypes.c_uint32)]
+
+
+class FrameSwitchParams(ctypes.Structure):
+    """sml_frame_switch_params (include/switchml_hip.h)."""
+    _fields_ = [("switch_mac", ctypes.c_uint8 * 6), ("switch_ip_be", ctypes.c_uint32),
+                ("num_workers", ctypes.c_uint16), ("num_slots", ctypes.c_uint32),
+                ("packet_numel", ctypes.c_uint32), ("workers", SwitchWorker * MAX_FRAME_SWITCH_WORKERS)]
+
+
+def frame_switch_params(workers, num_slots: int, packet_numel: int = 256, switch_mac=b"\x02\x00\x00\x00\x00\x01",
+                        switch_ip="10.0.0.253") -> FrameSwitchParams:
+    """`workers`: a (mac bytes, dotted IPv4 string) pair per worker, in worker-id order."""
+    import socket
+    import struct
+    workers = list(workers)
+    if len(workers) > MAX_FRAME_SWITCH_WORKERS:
+        raise ValueError(f"at most {MAX_FRAME_SWITCH_WORKERS} workers (worker_bitmap_t is 32 bits)")
+    sp = FrameSwitchParams()
+    sp.switch_mac[:] = list(switch_mac)
+    sp.switch_ip_be = struct.unpack("<I", socket.inet_aton(switch_ip))[0]
+    sp.num_workers = len(workers)
+    sp.num_slots = num_slots
+    sp.packet_numel = packet_numel
+    for i, (mac, ip) in enumerate(workers):
+        sp.workers[i].mac[:] = list(mac)
+        sp.workers[i].ip_be = struct.unpack("<I", socket.inet_aton(ip))[0]
+    return sp
+
+
 MAX_BURST = 64
 
 
@@ -159,6 +197,12 @@ def lib():
     L.sml_pack_frames_int32.argtypes = [vp, u64, u32, ctypes.POINTER(FrameParams), vp, u64, vp]
     L.sml_unpack_frames_int32.restype = i32
     L.sml_unpack_frames_int32.argtypes = [vp, u64, u64, u64, u32, u64, vp, vp, vp, vp]
+    L.sml_frame_switch_state_bytes.restype = u64
+    L.sml_frame_switch_state_bytes.argtypes = [u32, u32]
+    L.sml_frame_switch_reset.restype = i32
+    L.sml_frame_switch_reset.argtypes = [vp, u32, u32, vp]
+    L.sml_frame_switch.restype = i32
+    L.sml_frame_switch.argtypes = [ctypes.POINTER(FrameSwitchParams), vp, u64, u64, vp, vp, u64, vp, vp, vp]
     L.sml_switch_aggregate.restype = i32
     L.sml_switch_aggregate.argtypes = [vp, vp, u16, u64, u32, vp, vp, vp, u32, vp]
     L.sml_exponents_typed.restype = i32
@@ -872,6 +916,56 @@ def unpack_frames_int32(frames, num_frames: int, rx: RxSliceInt32, job_id: int =
         _dev(rx.state, torch.int64, "state"), _dev(rx.out, torch.int32, "out"),
         _dev(rx.counts, torch.int64, "counts"), _stream(stream, rx.out)))
     return rx.out
+
+
+class FrameSwitch:
+    """The switch between DPDK workers (sml_frame_switch): owns the slot
+    pool's registers on the device and aggregates a batch of arrived frames
+    per call.  `workers`: a (mac bytes, dotted IPv4) pair per worker, or a
+    ready FrameSwitchParams as `params`."""
+
+    def __init__(self, workers=None, num_slots: int = 64, packet_numel: int = 256, device="cuda",
+                 switch_mac=b"\x02\x00\x00\x00\x00\x01", switch_ip="10.0.0.253", params=None):
+        torch = _torch()
+        self.params = params if params is not None else frame_switch_params(
+            workers, num_slots, packet_numel, switch_mac=switch_mac, switch_ip=switch_ip)
+        self.packet_numel = int(self.params.packet_numel)
+        self.num_slots = int(self.params.num_slots)
+        nbytes = int(lib().sml_frame_switch_state_bytes(self.num_slots, self.packet_numel))
+        if nbytes == 0:
+            raise SwitchMLError("sml_frame_switch_state_bytes", SML_ERR_UNSUPPORTED)
+        self.state = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+        self.counts = torch.zeros(5, dtype=torch.int64, device=device)
+        self.reset()
+
+    def reset(self, stream=None):
+        """Clear the switch's registers: every slot empty, both sets (sml_frame_switch_reset)."""
+        torch = _torch()
+        _check("sml_frame_switch_reset", lib().sml_frame_switch_reset(
+            _dev(self.state, torch.int64, "state"), self.num_slots, self.packet_numel, _stream(stream, self.state)))
+
+    def __call__(self, frames, num_frames: int, out=None, stride: int | None = None, out_stride: int | None = None,
+                 verdict=None, stream=None):
+        """Aggregate `num_frames` arrived frames (`stride` bytes apart; device
+        or pinned host memory).  Returns (out, verdict, counts): the result
+        frame of input frame i at out[i * out_stride:] where verdict[i] is
+        VERDICT_BROADCAST or VERDICT_RETRANSMIT (other positions keep their
+        bytes), the uint8 verdicts, and the switch's running per-verdict
+        counters.  VERDICT_DEFERRED frames are to be resubmitted in a later call."""
+        torch = _torch()
+        stride = stride or frame_bytes(self.packet_numel)
+        out_stride = out_stride or stride
+        dev = self.state.device
+        if out is None:
+            out = torch.zeros(max(1, num_frames) * out_stride, dtype=torch.uint8, device=dev)
+        if verdict is None:
+            verdict = torch.empty(max(1, num_frames), dtype=torch.uint8, device=dev)
+        _check("sml_frame_switch", lib().sml_frame_switch(
+            ctypes.byref(self.params), _dev(frames, torch.uint8, "frames"), num_frames, stride,
+            _dev(self.state, torch.int64, "state"), _dev(out, torch.uint8, "out"), out_stride,
+            _dev(verdict, torch.uint8, "verdict"), _dev(self.counts, torch.int64, "counts"),
+            _stream(stream, self.state)))
+        return out, verdict[:num_frames], self.counts
 
 
 def debug_stall(microseconds: int, stream=None):
