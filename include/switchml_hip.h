@@ -690,6 +690,73 @@ sml_status_t sml_frame_switch(const sml_frame_switch_params* params,
                               void* d_state, void* out_frames, uint64_t out_stride,
                               uint8_t* d_verdict, uint64_t* d_counts, void* stream);
 
+/* The egress of one sml_frame_switch call (above): the multicast group of
+ * p4/next_step_selector.p4 and p4/udp_sender.p4's per-port destination, into
+ * one receive ring per worker.  out_frames / num_frames / out_stride /
+ * d_verdict are what that call left; worker u's ring starts at rings +
+ * u * ring_bytes and holds up to ring_frames frames rx_stride bytes apart — a
+ * dense run, as sml_dequantize_frames / sml_unpack_frames_int32 take it.
+ *   The input frames i in ascending order:
+ *   BROADCAST: a copy for every worker u in 0..num_workers-1, out_frames[i]
+ *     with bytes 0-5 = workers[u].mac, bytes 30-33 = workers[u].ip_be and bytes
+ *     24-25 = the IPv4 header checksum of sml_frame_switch's result header to
+ *     worker u; every other byte, ports included, unchanged (the copy for the
+ *     worker the switch addressed the frame to is out_frames[i] byte for byte);
+ *   RETRANSMIT: one copy, unchanged, for the first worker whose ip_be equals
+ *     bytes 30-33; no such worker: nothing, counted `unroutable`;
+ *   any other verdict: nothing, out_frames[i] is not read.
+ *   A copy whose bit in d_drop[i] is set (bit u = the copy for worker u) is not
+ *   written and is counted `dropped`.  A surviving copy is appended to worker
+ *   u's ring at position d_ring_count[u] + (the surviving copies for u from
+ *   frames below i in this call): each ring holds its worker's frames in
+ *   ascending input order behind what earlier calls left (per-port FIFO; the
+ *   order is part of the contract).  Positions >= ring_frames are not written
+ *   and are counted `overflow`; d_ring_count[u] ends at min(old + survivors,
+ *   ring_frames).  No other byte of a ring is touched.
+ *   rings: device memory or pinned, device-mapped host memory, 4-byte aligned;
+ *     rx_stride >= sml_frame_bytes(P), ring_bytes >= ring_frames * rx_stride,
+ *     both multiples of 4;
+ *   d_drop: uint32[num_frames] or NULL (nothing dropped); d_ring_count:
+ *     uint64[num_workers], in / out; d_counts: uint64[4] {delivered, dropped,
+ *     overflow, unroutable}, added to, nullable; device memory, 8-byte aligned
+ *     (d_drop 4);
+ *   d_scratch: sml_frame_switch_deliver_scratch_bytes(num_frames, num_workers)
+ *     bytes of device memory, 16-byte aligned, contents free between calls (the
+ *     per-frame copy sets and the per-worker prefix counts of the call).
+ * Status, every check before any launch: params NULL, num_workers == 0, or
+ * (num_frames > 0) a NULL out_frames / d_verdict / rings / d_ring_count /
+ * d_scratch -> SML_ERR_INVALID_ARG; packet_numel not a packet size,
+ * num_workers > SML_MAX_FRAME_SWITCH_WORKERS, ring_frames == 0, num_frames >=
+ * 2^31 -> SML_ERR_UNSUPPORTED; num_frames == 0 -> SML_OK, nothing launched; a
+ * buffer or stride off its alignment, or ring_bytes < ring_frames * rx_stride
+ * -> SML_ERR_ALIGNMENT.
+ * Three launches on `stream`: counts (thread per frame, a wave ballot per
+ * worker), the scan of the counts (workgroup per worker), the copy (wave per
+ * input frame; it reads a frame once and writes its copies). */
+uint64_t sml_frame_switch_deliver_scratch_bytes(uint64_t num_frames, uint32_t num_workers);
+sml_status_t sml_frame_switch_deliver(const sml_frame_switch_params* params,
+                                      const void* out_frames, uint64_t num_frames, uint64_t out_stride,
+                                      const uint8_t* d_verdict, const uint32_t* d_drop,
+                                      void* rings, uint64_t ring_bytes, uint64_t ring_frames, uint64_t rx_stride,
+                                      uint64_t* d_ring_count, uint64_t* d_counts, void* d_scratch, void* stream);
+
+/* The ingress of a sml_frame_switch call: its input from the workers' tx
+ * frame sets.  sets: a host array of num_sets <= 32 base pointers (device or
+ * pinned, device-mapped memory, 4-byte aligned), each set_frames frames
+ * set_stride bytes apart.  Output frame j (dst + j * dst_stride) is the
+ * sml_frame_bytes(P) bytes of frame d_index[j] of set d_set[j]; an entry with
+ * d_set[j] >= num_sets or d_index[j] >= set_frames writes nothing and adds 1
+ * to *d_skipped (device uint64, nullable).  d_set: uint32[n], d_index:
+ * uint64[n], device memory.  One launch on `stream`, a wave per frame.
+ * Status: sets NULL, num_sets == 0, or (n > 0) a NULL d_set / d_index / dst /
+ * entry of sets -> SML_ERR_INVALID_ARG; packet_numel not a packet size or
+ * num_sets > 32 -> SML_ERR_UNSUPPORTED; n == 0 -> SML_OK, nothing launched; a
+ * buffer or stride off its alignment (strides >= sml_frame_bytes(P), multiples
+ * of 4; d_index and d_skipped 8-byte aligned) -> SML_ERR_ALIGNMENT. */
+sml_status_t sml_frame_gather(const void* const* sets, uint32_t num_sets, uint64_t set_frames, uint64_t set_stride,
+                              const uint32_t* d_set, const uint64_t* d_index, uint64_t n, uint32_t packet_numel,
+                              void* dst, uint64_t dst_stride, uint64_t* d_skipped, void* stream);
+
 /* ncclUint8 buckets of the CollNet plugin (switchml_plugin.cc:318-337,
  * 370-378: "SwitchML does not really support uint8"): each byte widened to an
  * int32 for the INT32 all-reduce, and the summed words narrowed back (mod

@@ -31,6 +31,11 @@
 // else ~((frame << 1) | set), so atomicMax keeps the lowest frame); per
 // (slot, set) bitmap, count and exponent pair (uint32 each); the touched list
 // uint32[S]; the accumulators uint32[S][2][P] in host order.
+//
+// The wire on both sides of a call is below the switch: sml_frame_gather
+// builds a call's input from the workers' tx frame sets ("ingress"), and
+// sml_frame_switch_deliver replicates the results into one receive ring per
+// worker ("egress").
 #include "sml_host.h"
 
 namespace sml {
@@ -362,6 +367,271 @@ static uint32_t fs_ipv4_checksum(uint32_t total_len, uint32_t src_ip, uint32_t d
     return (ck >> 8) | ((ck & 0xffu) << 8);
 }
 
+// The worker table of FsArgs / FdArgs: MAC, address and the IPv4 header
+// checksum of a result frame to each worker.
+static void fs_worker_table(const sml_frame_switch_params& prm, FsWorker* tbl) {
+    const uint32_t total_len = (uint32_t)sml_frame_bytes(prm.packet_numel) - 14;
+    for (uint32_t u = 0; u < prm.num_workers; u++) {
+        const sml_switch_worker& wk = prm.workers[u];
+        memcpy(&tbl[u].mac_lo, wk.mac, 4);
+        tbl[u].mac_hi_ck = (uint32_t)wk.mac[4] | ((uint32_t)wk.mac[5] << 8) |
+                           (fs_ipv4_checksum(total_len, prm.switch_ip_be, wk.ip_be) << 16);
+        tbl[u].ip = wk.ip_be;
+    }
+}
+
+// ------------------------------------------------------------------ egress
+// sml_frame_switch_deliver: the multicast group of next_step_selector.p4 and
+// udp_sender.p4's per-port rewrite, into one receive ring per worker.  The
+// position of a copy in its ring is a per-worker exclusive prefix count over
+// the call's frames — a grid-wide dependency, taken in three launches:
+//   k_fd_count  thread per frame: the set of workers that get a copy (verdict,
+//               the asker's address for a RETRANSMIT, the drop mask) goes to
+//               masks[f]; a wave ballot per worker counts the copies of the
+//               wave's kFdGroup frames into counts[u][group].
+//   k_fd_scan   workgroup per worker: its row of group counts becomes the
+//               exclusive prefix, kFdScanTile groups a step with a carry; the
+//               ring count as the call found it is kept in base[u] and
+//               d_ring_count[u] advances; delivered / overflow are counted.
+//   k_fd_copy   wave per input frame: the masks of the frames below it in its
+//               group give, with a ballot per copy, the position; the frame is
+//               read once and stored once per copy, a BROADCAST's destination
+//               MAC, address and checksum replaced from the worker table.
+// No workgroup waits on another and no atomic decides a position: every ring
+// position, count word and prefix word has one writer per launch.
+constexpr int kFdGroup = kWave;                              // frames per count group
+constexpr int kFdScanPer = 4;                                // groups per scan thread
+constexpr int kFdScanTile = kBlockThreads * kFdScanPer;      // groups per scan step
+constexpr uint64_t kFdHead = 8 * kFsMaxWorkers;              // scratch bytes before the masks
+
+struct FdArgs {
+    const uint8_t* out;             // sml_frame_switch's out_frames
+    uint64_t nframes;
+    uint64_t out_stride;
+    const uint8_t* verdict;
+    const uint32_t* drop;           // nullable
+    uint8_t* rings;
+    uint64_t ring_bytes, ring_frames, rx_stride;
+    unsigned long long* ring_count; // [W]
+    unsigned long long* counts;     // [4] or nullptr
+    unsigned long long* base;       // scratch [32]: ring_count as the call found it
+    uint32_t* masks;                // scratch [nframes]: bit u = worker u gets a copy
+    uint32_t* prefix;               // scratch [W][group_stride]: counts, then their exclusive prefix
+    uint64_t ngroups;               // ceil(nframes / kFdGroup)
+    uint64_t group_stride;
+    uint32_t W;
+    FsWorker workers[kFsMaxWorkers];
+};
+
+// Pass 1.  Workgroup b takes frames [256 b, 256 b + 256): a wave's frames are
+// one group.
+__global__ __launch_bounds__(kBlockThreads) void k_fd_count(FdArgs a) {
+    __shared__ uint32_t lost[2];                               // dropped, unroutable
+    if (threadIdx.x < 2) lost[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t all = 0xffffffffu >> (32 - a.W);
+    const uint64_t nblocks = (a.nframes + kBlockThreads - 1) / kBlockThreads;
+    for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const uint64_t f = b * kBlockThreads + threadIdx.x;
+        uint32_t mask = 0, dropped = 0;
+        bool unroutable = false;
+        if (f < a.nframes) {
+            const uint32_t vd = a.verdict[f];
+            if (vd == SML_VERDICT_BROADCAST) {
+                mask = all;
+            } else if (vd == SML_VERDICT_RETRANSMIT) {
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(a.out + f * a.out_stride);
+                const uint32_t ip = (p[7] >> 16) | (p[8] << 16);               // bytes 30-33
+                for (uint32_t u = 0; u < a.W; u++) mask = (a.workers[u].ip == ip && mask == 0u) ? 1u << u : mask;
+                unroutable = mask == 0u;
+            }
+            const uint32_t dm = (a.drop && mask) ? a.drop[f] : 0u;
+            dropped = (uint32_t)__builtin_popcount(mask & dm);
+            mask &= ~dm;
+            a.masks[f] = mask;
+        }
+        uint32_t mine = 0;                                     // lane u: worker u's copies in this group
+        for (uint32_t u = 0; u < a.W; u++) {
+            const uint32_t c = (uint32_t)__builtin_popcountll(__ballot((mask >> u) & 1u));
+            mine = lane == u ? c : mine;
+        }
+        const uint64_t g = b * kWavesPerBlock + wave_index();
+        if (lane < a.W && g < a.ngroups) a.prefix[lane * a.group_stride + g] = mine;
+        if (a.counts) {
+            if (dropped) atomicAdd(&lost[0], dropped);
+            if (unroutable) atomicAdd(&lost[1], 1u);
+        }
+    }
+    if (!a.counts) return;
+    __syncthreads();
+    if (threadIdx.x < 2 && lost[threadIdx.x])
+        atomicAdd(a.counts + (threadIdx.x == 0 ? 1 : 3), (unsigned long long)lost[threadIdx.x]);
+}
+
+// Pass 2, workgroup u: worker u's group counts -> their exclusive prefix, in
+// place; then the ring's count moves on.
+__global__ __launch_bounds__(kBlockThreads) void k_fd_scan(FdArgs a) {
+    __shared__ uint32_t wtot[kWavesPerBlock];
+    const uint32_t u = blockIdx.x;
+    const uint32_t lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    uint32_t* const row = a.prefix + (uint64_t)u * a.group_stride;
+    uint32_t carry = 0;
+    for (uint64_t t0 = 0; t0 < a.ngroups; t0 += kFdScanTile) {
+        const uint64_t g0 = t0 + (uint64_t)threadIdx.x * kFdScanPer;
+        uint32_t c[kFdScanPer], s = 0;
+#pragma unroll
+        for (int k = 0; k < kFdScanPer; k++) {
+            c[k] = g0 + k < a.ngroups ? row[g0 + k] : 0u;
+            s += c[k];
+        }
+        uint32_t inc = s;                                      // inclusive over the wave's threads
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)inc, d);
+            inc += (int)lane >= d ? o : 0u;
+        }
+        if (lane == kWave - 1) wtot[wv] = inc;
+        __syncthreads();
+        uint32_t x = carry + inc - s, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < (uint32_t)kWavesPerBlock; w++) {
+            x += w < wv ? wtot[w] : 0u;
+            total += wtot[w];
+        }
+#pragma unroll
+        for (int k = 0; k < kFdScanPer; k++) {
+            if (g0 + k < a.ngroups) row[g0 + k] = x;
+            x += c[k];
+        }
+        carry += total;
+        __syncthreads();                                       // wtot is the next step's too
+    }
+    if (threadIdx.x == 0) {
+        const uint64_t old = a.ring_count[u], end = old + carry;
+        const uint64_t over = old >= a.ring_frames ? carry : end > a.ring_frames ? end - a.ring_frames : 0;
+        a.base[u] = old;
+        a.ring_count[u] = end < a.ring_frames ? end : a.ring_frames;
+        if (a.counts) {
+            if (carry - over) atomicAdd(a.counts + 0, (unsigned long long)(carry - over));
+            if (over) atomicAdd(a.counts + 2, (unsigned long long)over);
+        }
+    }
+}
+
+// The 52 header bytes (a dword in each of lanes 0-12) and the payload's
+// 16-byte chunks of the frame at `in`, the way k_fs_result lays a frame over a
+// wave.  A lane past the payload (P < 256) rereads chunk 0 and drops it.
+template <int P>
+struct FrameRegs {
+    static constexpr int kChunks = P / 4;
+    static constexpr int kPer = (kChunks + kWave - 1) / kWave;
+    uint32_t dw;
+    u4a w[kPer];
+
+    __device__ __forceinline__ void load(const uint8_t* in, int lane) {
+        dw = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(in) + (lane < 13 ? lane : 0));
+#pragma unroll
+        for (int k = 0; k < kPer; k++) {
+            const int ch = k * kWave + lane;
+            w[k] = __builtin_nontemporal_load(reinterpret_cast<const u4a*>(in + 52 + 16 * (ch < kChunks ? ch : 0)));
+        }
+    }
+    // Non-temporal at the 52-byte offset: plain `nt`, not `sc1 nt`.
+    __device__ __forceinline__ void store(uint8_t* o, int lane, uint32_t header) const {
+        if (lane < 13) reinterpret_cast<uint32_t*>(o)[lane] = header;
+#pragma unroll
+        for (int k = 0; k < kPer; k++) {
+            const int ch = k * kWave + lane;
+            if (ch < kChunks) SML_NT_STORE16_UNALIGNED(w[k], reinterpret_cast<u4a*>(o + 52 + 16 * ch));
+        }
+    }
+};
+
+// Pass 3, wave per input frame (a wave whose frame has no copy ends after its
+// group's mask load).
+template <int P>
+__global__ __launch_bounds__(kBlockThreads) void k_fd_copy(FdArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
+    for (uint64_t f = (uint64_t)blockIdx.x * kWavesPerBlock + wave_index(); f < a.nframes; f += nwaves) {
+        const uint64_t g = f / kFdGroup, f0 = g * kFdGroup;
+        const uint32_t at = (uint32_t)(f - f0);
+        const uint32_t m = f0 + lane < a.nframes ? a.masks[f0 + lane] : 0u;
+        const uint32_t own = (uint32_t)__builtin_amdgcn_readlane((int)m, (int)at);
+        if (own == 0u) continue;
+        const uint32_t below = (uint32_t)lane < at ? m : 0u;   // the group's frames before this one
+        const bool bcast = a.verdict[f] == SML_VERDICT_BROADCAST;
+        FrameRegs<P> fr;
+        fr.load(a.out + f * a.out_stride, lane);
+        for (uint32_t rest = own; rest; rest &= rest - 1) {
+            const uint32_t u = (uint32_t)__builtin_ctz(rest);
+            const uint64_t pos = a.base[u] + a.prefix[u * a.group_stride + g] +
+                                 (uint64_t)__builtin_popcountll(__ballot((below >> u) & 1u));
+            if (pos >= a.ring_frames) continue;                // overflow: counted by the scan
+            uint32_t dw = fr.dw;
+            if (bcast) {                                       // RETRANSMIT: the asker's frame as it is
+                const FsWorker wk = a.workers[u];
+                dw = lane == 0 ? wk.mac_lo : dw;                                                 // bytes 0-3
+                dw = lane == 1 ? ((dw & 0xffff0000u) | (wk.mac_hi_ck & 0xffffu)) : dw;           // 4-5
+                dw = lane == 6 ? ((dw & 0xffff0000u) | (wk.mac_hi_ck >> 16)) : dw;               // 24-25
+                dw = lane == 7 ? ((dw & 0x0000ffffu) | (wk.ip << 16)) : dw;                      // 30-31
+                dw = lane == 8 ? ((dw & 0xffff0000u) | (wk.ip >> 16)) : dw;                      // 32-33
+            }
+            fr.store(a.rings + u * a.ring_bytes + pos * a.rx_stride, lane, dw);
+        }
+    }
+}
+
+// ----------------------------------------------------------------- ingress
+// sml_frame_gather: a switch call's input from the workers' tx frame sets, a
+// wave per output frame.
+struct FgArgs {
+    const uint8_t* sets[kFsMaxWorkers];
+    uint32_t num_sets;
+    uint64_t set_frames, set_stride;
+    const uint32_t* set;
+    const unsigned long long* index;
+    uint64_t n;
+    uint8_t* dst;
+    uint64_t dst_stride;
+    unsigned long long* skipped;    // nullable
+};
+
+template <int P>
+__global__ __launch_bounds__(kBlockThreads) void k_fg_gather(FgArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
+    for (uint64_t j = (uint64_t)blockIdx.x * kWavesPerBlock + wave_index(); j < a.n; j += nwaves) {
+        const uint32_t s = a.set[j];
+        const uint64_t i = a.index[j];
+        if (s >= a.num_sets || i >= a.set_frames) {
+            if (lane == 0 && a.skipped) atomicAdd(a.skipped, 1ull);
+            continue;
+        }
+        FrameRegs<P> fr;
+        fr.load(a.sets[s] + i * a.set_stride, lane);
+        fr.store(a.dst + j * a.dst_stride, lane, fr.dw);
+    }
+}
+
+// The pieces of sml_frame_switch_deliver's d_scratch.
+struct FdLayout {
+    uint64_t masks, prefix, ngroups, group_stride, total;
+};
+
+static FdLayout fd_layout(uint64_t num_frames, uint32_t W) {
+    FdLayout l;
+    l.ngroups = (num_frames + kFdGroup - 1) / kFdGroup;
+    l.group_stride = (l.ngroups + 3) & ~3ull;
+    l.masks = kFdHead;
+    l.prefix = (l.masks + 4 * num_frames + 15) & ~15ull;
+    l.total = l.prefix + 4ull * W * l.group_stride;
+    return l;
+}
+
+constexpr uint64_t kFdMaxFrames = 0x7fffffffull;               // positions and counts of a call fit 32 bits
+
 }  // namespace sml
 
 using namespace sml;
@@ -421,13 +691,7 @@ sml_status_t sml_frame_switch(const sml_frame_switch_params* prm, const void* fr
     const uint32_t total_len = (uint32_t)fb - 14, udp_len = (uint32_t)fb - 34;
     a.len_dw4 = (total_len >> 8) | ((total_len & 0xffu) << 8);
     a.udp_len_be = (udp_len >> 8) | ((udp_len & 0xffu) << 8);
-    for (uint32_t u = 0; u < W; u++) {
-        const sml_switch_worker& wk = prm->workers[u];
-        memcpy(&a.workers[u].mac_lo, wk.mac, 4);
-        a.workers[u].mac_hi_ck = (uint32_t)wk.mac[4] | ((uint32_t)wk.mac[5] << 8) |
-                                 (fs_ipv4_checksum(total_len, prm->switch_ip_be, wk.ip_be) << 16);
-        a.workers[u].ip = wk.ip_be;
-    }
+    fs_worker_table(*prm, a.workers);
 
     hipStream_t st = (hipStream_t)stream;
     const uint32_t gframes = grid_for_vec(num_frames);
@@ -441,6 +705,94 @@ sml_status_t sml_frame_switch(const sml_frame_switch_params* prm, const void* fr
         k_fs_apply<Pc()><<<gslots, kBlockThreads, 0, st>>>(a);
         k_fs_result<Pc()><<<gresult, kBlockThreads, 0, st>>>(a);
     });
+    return launch_check();
+}
+
+uint64_t sml_frame_switch_deliver_scratch_bytes(uint64_t num_frames, uint32_t num_workers) {
+    if (num_workers == 0 || num_workers > kFsMaxWorkers || num_frames > kFdMaxFrames) return 0;
+    return fd_layout(num_frames, num_workers).total;
+}
+
+sml_status_t sml_frame_switch_deliver(const sml_frame_switch_params* prm, const void* out_frames,
+                                      uint64_t num_frames, uint64_t out_stride, const uint8_t* d_verdict,
+                                      const uint32_t* d_drop, void* rings, uint64_t ring_bytes,
+                                      uint64_t ring_frames, uint64_t rx_stride, uint64_t* d_ring_count,
+                                      uint64_t* d_counts, void* d_scratch, void* stream) {
+    if (!prm || prm->num_workers == 0) return SML_ERR_INVALID_ARG;
+    if (num_frames && (!out_frames || !d_verdict || !rings || !d_ring_count || !d_scratch)) return SML_ERR_INVALID_ARG;
+    const uint32_t P = prm->packet_numel, W = prm->num_workers;
+    if (!valid_packet(P) || W > kFsMaxWorkers || ring_frames == 0 || num_frames > kFdMaxFrames)
+        return SML_ERR_UNSUPPORTED;
+    if (num_frames == 0) return SML_OK;
+    const uint64_t fb = sml_frame_bytes(P);
+    if (!aligned4(out_frames) || out_stride % 4 || out_stride < fb) return SML_ERR_ALIGNMENT;
+    if (!aligned4(rings) || rx_stride % 4 || rx_stride < fb || ring_bytes % 4) return SML_ERR_ALIGNMENT;
+    if (ring_frames > ~0ull / rx_stride || ring_bytes < ring_frames * rx_stride) return SML_ERR_ALIGNMENT;
+    if (!aligned4(d_drop) || ((uintptr_t)d_ring_count & 7u) || ((uintptr_t)d_counts & 7u) ||
+        ((uintptr_t)d_scratch & 15u))
+        return SML_ERR_ALIGNMENT;
+
+    const FdLayout l = fd_layout(num_frames, W);
+    uint8_t* const sc8 = static_cast<uint8_t*>(d_scratch);
+    FdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.out = static_cast<const uint8_t*>(out_frames);
+    a.nframes = num_frames;
+    a.out_stride = out_stride;
+    a.verdict = d_verdict;
+    a.drop = d_drop;
+    a.rings = static_cast<uint8_t*>(rings);
+    a.ring_bytes = ring_bytes;
+    a.ring_frames = ring_frames;
+    a.rx_stride = rx_stride;
+    a.ring_count = reinterpret_cast<unsigned long long*>(d_ring_count);
+    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
+    a.base = reinterpret_cast<unsigned long long*>(sc8);
+    a.masks = reinterpret_cast<uint32_t*>(sc8 + l.masks);
+    a.prefix = reinterpret_cast<uint32_t*>(sc8 + l.prefix);
+    a.ngroups = l.ngroups;
+    a.group_stride = l.group_stride;
+    a.W = W;
+    fs_worker_table(*prm, a.workers);
+
+    hipStream_t st = (hipStream_t)stream;
+    k_fd_count<<<grid_for_vec(num_frames), kBlockThreads, 0, st>>>(a);
+    k_fd_scan<<<W, kBlockThreads, 0, st>>>(a);
+    const uint32_t gcopy = grid_for_tiles(num_frames);
+    dispatch_packet(P, [&](auto Pc) { k_fd_copy<Pc()><<<gcopy, kBlockThreads, 0, st>>>(a); });
+    return launch_check();
+}
+
+sml_status_t sml_frame_gather(const void* const* sets, uint32_t num_sets, uint64_t set_frames, uint64_t set_stride,
+                              const uint32_t* d_set, const uint64_t* d_index, uint64_t n, uint32_t packet_numel,
+                              void* dst, uint64_t dst_stride, uint64_t* d_skipped, void* stream) {
+    if (!sets || num_sets == 0) return SML_ERR_INVALID_ARG;
+    if (n && (!d_set || !d_index || !dst)) return SML_ERR_INVALID_ARG;
+    if (!valid_packet(packet_numel) || num_sets > kFsMaxWorkers) return SML_ERR_UNSUPPORTED;
+    if (n == 0) return SML_OK;
+    for (uint32_t s = 0; s < num_sets; s++)
+        if (!sets[s]) return SML_ERR_INVALID_ARG;
+    const uint64_t fb = sml_frame_bytes(packet_numel);
+    for (uint32_t s = 0; s < num_sets; s++)
+        if (!aligned4(sets[s])) return SML_ERR_ALIGNMENT;
+    if (set_stride % 4 || set_stride < fb) return SML_ERR_ALIGNMENT;
+    if (!aligned4(dst) || dst_stride % 4 || dst_stride < fb) return SML_ERR_ALIGNMENT;
+    if (!aligned4(d_set) || ((uintptr_t)d_index & 7u) || ((uintptr_t)d_skipped & 7u)) return SML_ERR_ALIGNMENT;
+
+    FgArgs a;
+    memset(&a, 0, sizeof(a));
+    for (uint32_t s = 0; s < num_sets; s++) a.sets[s] = static_cast<const uint8_t*>(sets[s]);
+    a.num_sets = num_sets;
+    a.set_frames = set_frames;
+    a.set_stride = set_stride;
+    a.set = d_set;
+    a.index = reinterpret_cast<const unsigned long long*>(d_index);
+    a.n = n;
+    a.dst = static_cast<uint8_t*>(dst);
+    a.dst_stride = dst_stride;
+    a.skipped = reinterpret_cast<unsigned long long*>(d_skipped);
+    const uint32_t grid = grid_for_tiles(n);
+    dispatch_packet(packet_numel, [&](auto Pc) { k_fg_gather<Pc()><<<grid, kBlockThreads, 0, (hipStream_t)stream>>>(a); });
     return launch_check();
 }
 

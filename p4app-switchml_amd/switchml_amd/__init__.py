@@ -9,6 +9,7 @@ call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import re
@@ -203,6 +204,13 @@ def lib():
     L.sml_frame_switch_reset.argtypes = [vp, u32, u32, vp]
     L.sml_frame_switch.restype = i32
     L.sml_frame_switch.argtypes = [ctypes.POINTER(FrameSwitchParams), vp, u64, u64, vp, vp, u64, vp, vp, vp]
+    L.sml_frame_switch_deliver_scratch_bytes.restype = u64
+    L.sml_frame_switch_deliver_scratch_bytes.argtypes = [u64, u32]
+    L.sml_frame_switch_deliver.restype = i32
+    L.sml_frame_switch_deliver.argtypes = [ctypes.POINTER(FrameSwitchParams), vp, u64, u64, vp, vp, vp, u64, u64, u64,
+                                           vp, vp, vp, vp]
+    L.sml_frame_gather.restype = i32
+    L.sml_frame_gather.argtypes = [ctypes.POINTER(vp), u32, u64, u64, vp, vp, u64, u32, vp, u64, vp, vp]
     L.sml_switch_aggregate.restype = i32
     L.sml_switch_aggregate.argtypes = [vp, vp, u16, u64, u32, vp, vp, vp, u32, vp]
     L.sml_exponents_typed.restype = i32
@@ -936,6 +944,11 @@ class FrameSwitch:
             raise SwitchMLError("sml_frame_switch_state_bytes", SML_ERR_UNSUPPORTED)
         self.state = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
         self.counts = torch.zeros(5, dtype=torch.int64, device=device)
+        # the egress (deliver): the workers' receive rings and their fill counts
+        self.rings = None
+        self.ring_count = torch.zeros(int(self.params.num_workers), dtype=torch.int64, device=device)
+        self.deliver_counts = torch.zeros(4, dtype=torch.int64, device=device)
+        self._scratch = None
         self.reset()
 
     def reset(self, stream=None):
@@ -966,6 +979,97 @@ class FrameSwitch:
             _dev(verdict, torch.uint8, "verdict"), _dev(self.counts, torch.int64, "counts"),
             _stream(stream, self.state)))
         return out, verdict[:num_frames], self.counts
+
+    def reset_rings(self, stream=None):
+        """Empty every worker's receive ring: the ring counts and the delivery
+        counters go to zero (the rings keep their bytes)."""
+        torch = _torch()
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+        with ctx:
+            self.ring_count.zero_()
+            self.deliver_counts.zero_()
+
+    def deliver(self, out, verdict, num_frames: int, rings=None, ring_frames: int | None = None, drop=None,
+                out_stride: int | None = None, rx_stride: int | None = None, ring_bytes: int | None = None,
+                ring_count=None, stream=None):
+        """The egress of one call (sml_frame_switch_deliver): `out` / `verdict`
+        as __call__ returned them; every BROADCAST is appended to every
+        worker's ring, addressed to that worker, every RETRANSMIT to its
+        asker's, in input order behind what earlier calls left.  `rings`:
+        uint8 [W, ring_frames, rx_stride] (device or pinned host memory), or
+        any contiguous uint8 tensor with `ring_frames`, `rx_stride` and
+        `ring_bytes` given; None = the switch's own (allocated on first use,
+        `ring_frames` frames per worker).  `drop`: int32 [num_frames], bit u =
+        the copy for worker u is lost.  `ring_count`: int64 [W], default the
+        switch's own.  Returns (rings, ring_count, counts) with counts =
+        {delivered, dropped, overflow, unroutable}, running."""
+        torch = _torch()
+        fb = frame_bytes(self.packet_numel)
+        W = int(self.params.num_workers)
+        dev = self.state.device
+        if rings is None:
+            rings = self.rings
+        if rings is None:
+            if not ring_frames:
+                raise ValueError("ring_frames is needed to allocate the rings")
+            rings = torch.zeros((W, ring_frames, rx_stride or fb), dtype=torch.uint8, device=dev)
+        if rings.dim() == 3:
+            ring_frames = ring_frames or rings.shape[1]
+            rx_stride = rx_stride or rings.shape[2]
+            ring_bytes = ring_bytes or rings.shape[1] * rings.shape[2]
+        rx_stride = rx_stride or fb
+        if not ring_frames:
+            raise ValueError("ring_frames is needed for rings that are not [W, ring_frames, rx_stride]")
+        ring_bytes = ring_bytes or ring_frames * rx_stride
+        if rings.numel() < (W - 1) * ring_bytes + ring_frames * rx_stride:
+            raise ValueError("rings is smaller than W rings of ring_bytes")
+        self.rings = rings
+        ring_count = ring_count if ring_count is not None else self.ring_count
+        need = int(lib().sml_frame_switch_deliver_scratch_bytes(num_frames, W))
+        if self._scratch is None or self._scratch.numel() * 8 < need:
+            self._scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        d = None if drop is None else _dev(drop, torch.int32, "drop")
+        _check("sml_frame_switch_deliver", lib().sml_frame_switch_deliver(
+            ctypes.byref(self.params), _dev(out, torch.uint8, "out"), num_frames, out_stride or fb,
+            _dev(verdict, torch.uint8, "verdict"), d, _dev(rings, torch.uint8, "rings"), ring_bytes, ring_frames,
+            rx_stride, _dev(ring_count, torch.int64, "ring_count"), _dev(self.deliver_counts, torch.int64, "counts"),
+            _dev(self._scratch, torch.int64, "scratch"), _stream(stream, self.state)))
+        return rings, ring_count, self.deliver_counts
+
+
+def gather_frames(sets, set_idx, frame_idx, packet_numel: int = 256, set_frames: int | None = None,
+                  set_stride: int | None = None, out=None, out_stride: int | None = None, skipped=None, stream=None):
+    """One switch call's input from the workers' tx frame sets
+    (sml_frame_gather): output frame j = frame frame_idx[j] (int64) of
+    sets[set_idx[j]] (int32).  `sets`: up to 32 uint8 tensors (device or pinned
+    host memory) of `set_frames` frames `set_stride` bytes apart (default:
+    packed, as many as the smallest set holds).  An entry out of range writes
+    nothing and adds 1 to `skipped` (int64 [1], device).  Returns (out, skipped)."""
+    torch = _torch()
+    fb = frame_bytes(packet_numel)
+    set_stride = set_stride or fb
+    out_stride = out_stride or fb
+    sets = list(sets)
+    if not sets:
+        raise ValueError("at least one set")
+    if set_frames is None:
+        set_frames = min(s.numel() // set_stride for s in sets)
+    elif any(s.numel() < (set_frames - 1) * set_stride + fb for s in sets):
+        raise ValueError("a set is smaller than set_frames frames")
+    n = set_idx.numel()
+    if frame_idx.numel() != n:
+        raise ValueError("set_idx and frame_idx differ in length")
+    dev = set_idx.device
+    if out is None:
+        out = torch.zeros(max(1, n) * out_stride, dtype=torch.uint8, device=dev)
+    if skipped is None:
+        skipped = torch.zeros(1, dtype=torch.int64, device=dev)
+    ptrs = (ctypes.c_void_p * len(sets))(*[_dev(s, torch.uint8, "sets").value for s in sets])
+    _check("sml_frame_gather", lib().sml_frame_gather(
+        ptrs, len(sets), set_frames, set_stride, _dev(set_idx, torch.int32, "set_idx"),
+        _dev(frame_idx, torch.int64, "frame_idx"), n, packet_numel, _dev(out, torch.uint8, "out"), out_stride,
+        _dev(skipped, torch.int64, "skipped"), _stream(stream, set_idx)))
+    return out, skipped
 
 
 def debug_stall(microseconds: int, stream=None):

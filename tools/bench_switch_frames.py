@@ -18,7 +18,11 @@ planes holding the same payload.  Interleaved rounds, medians with the rounds'
 min-max, HIP events around `reps` calls.  Before anything is timed, one call of
 each shape is checked: the verdict counts, and a result frame's words against
 the sum of its slot's payloads.
-Usage: bench_switch_frames.py [OUT.json]"""
+--deliver: the egress (sml_frame_switch_deliver) on the same two shapes, alone
+and behind the switch call, beside sml_stream_copy of its own algorithmic bytes
+(main_deliver below); --deliver-trace: a few untimed calls of those arms, to
+run under rocprofv3 --kernel-trace.
+Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace"""
 import json
 import os
 import statistics
@@ -169,5 +173,96 @@ def main(rounds=7, W=8, P=256):
     return 0
 
 
+def main_deliver(out_path=None, rounds=7, W=8, P=256, trace_only=False):
+    """The egress (sml_frame_switch_deliver) on the same two shapes: deliver
+    alone on one switch call's results, and switch + deliver, beside
+    sml_stream_copy of deliver's algorithmic bytes (R result frames read once,
+    W R copies written, the verdicts).  The rings are long enough for a timed
+    run's calls and are emptied (reset_rings) before each, so every call
+    appends and writes.  trace_only: a few untimed calls of each arm, for a
+    rocprofv3 --kernel-trace run of its own."""
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream()
+    fb = sw.frame_bytes(P)
+    shapes = {"window": (256, 2, 200), "batch": (16384, 4, 10)}     # num_slots, cycled frame sets, reps
+    if trace_only:
+        shapes = {k: (S, nb, 4) for k, (S, nb, _) in shapes.items()}
+    arms, meta = {}, {}
+    for name, (S, nbuf, reps) in shapes.items():
+        F = S * W
+        fs = sw.FrameSwitch(WORKERS, S, P, device=dev)
+        sets = [frame_set(S, W, P, k & 1, 60 + k, dev) for k in range(nbuf)]
+        out = torch.zeros(F * fb, dtype=torch.uint8, device=dev)
+        vd = torch.empty(F, dtype=torch.uint8, device=dev)
+        ring_frames = (reps + 4) * S
+        rings = torch.zeros((W, ring_frames, fb), dtype=torch.uint8, device=dev)
+        # checked before anything is timed: every ring gets the call's S results, addressed to its worker
+        fs(sets[0][0], F, out=out, verdict=vd)
+        fs.deliver(out, vd, F, rings=rings)
+        torch.cuda.synchronize()
+        assert fs.ring_count.tolist() == [S] * W and fs.deliver_counts.tolist() == [S * W, 0, 0, 0]
+        src_frames = out.view(F, fb)[vd == sw.VERDICT_BROADCAST]
+        for u in (0, W - 1):
+            got = rings[u, :S]
+            assert torch.equal(got[:, 34:], src_frames[:, 34:]) and bool((got[:, 33] == u + 1).all())
+        fs.reset()
+
+        def deliver_only(k, fs=fs, out=out, vd=vd, F=F, rings=rings):
+            fs.deliver(out, vd, F, rings=rings, stream=st)
+
+        def switch_deliver(k, fs=fs, sets=sets, nbuf=nbuf, out=out, vd=vd, F=F, rings=rings):
+            fs(sets[k % nbuf][0], F, out=out, verdict=vd, stream=st)
+            fs.deliver(out, vd, F, rings=rings, stream=st)
+
+        alg = S * fb + W * S * fb + F
+        half = (alg // 2 + 4095) // 4096 * 4096
+        src = [torch.empty(half, dtype=torch.uint8, device=dev).random_(0, 256) for _ in range(nbuf)]
+        dst = [torch.empty(half, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+
+        def copy(k, src=src, dst=dst, nbuf=nbuf):
+            sw.stream_copy(src[k % nbuf], dst[k % nbuf], stream=st)
+
+        # deliver alone runs on the results of the last switch call: switch_deliver leaves them in out / vd
+        arms[name + "_switch_deliver"] = (switch_deliver, reps, fs)
+        arms[name + "_deliver"] = (deliver_only, reps, fs)
+        arms[name + "_stream_copy"] = (copy, reps, None)
+        meta[name] = dict(frames_per_call=F, result_frames=S, copies_written=W * S, algorithmic_bytes=alg,
+                          copy_bytes_moved=2 * half)
+    times = {name: [] for name in arms}
+    step = [0]
+    for _ in range(1 if trace_only else rounds):
+        for name, (fn, reps, fs) in arms.items():
+            assert step[0] % 2 == 0 and reps % 2 == 0            # a switch's calls alternate its slots' sets
+            if fs is not None:
+                fs.reset_rings()
+            times[name].append(timed(fn, st, reps, step))
+    if trace_only:
+        return 0
+    res = {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+           for name, v in times.items()}
+    for name, m in meta.items():
+        us = statistics.median(times[name + "_deliver"])
+        cp = statistics.median(times[name + "_stream_copy"])
+        res[name + "_deliver"].update(m, TBps_algorithmic=round(m["algorithmic_bytes"] / us / 1e6, 3),
+                                      time_over_stream_copy=round(us / cp, 3))
+        res[name + "_stream_copy"].update(TBps=round(m["copy_bytes_moved"] / cp / 1e6, 3))
+    text = json.dumps({
+        "what": f"side measurement (not bench.py's headline): sml_frame_switch_deliver, W={W}, P={P}, on "
+                f"bench_switch_frames.py's two shapes (window: 256 slots, 2048 frames, 256 BROADCASTs; batch: 16384 "
+                f"slots, 131072 frames, 16384 BROADCASTs); deliver alone, switch + deliver, and sml_stream_copy of "
+                f"deliver's algorithmic bytes; {rounds} interleaved rounds, medians with the rounds' min-max, HIP "
+                f"events; nothing here was measured before this file was written",
+        "device": torch.cuda.get_device_name(0), "arms": res}, indent=1)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--deliver":
+        sys.exit(main_deliver(sys.argv[2] if len(sys.argv) > 2 else None))
+    if len(sys.argv) > 1 and sys.argv[1] == "--deliver-trace":
+        sys.exit(main_deliver(trace_only=True))
     sys.exit(main())
