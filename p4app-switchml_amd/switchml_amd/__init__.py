@@ -50,12 +50,12 @@ def frame_params(dst_mac=b"\x02\x00\x00\x00\x00\x01", src_mac=b"\x02\x00\x00\x00
                  src_ip="10.0.0.1", dst_ip="10.0.0.253", src_port=4000, dst_port=48879, job_id=0,
                  pool_index_start=0, pool_index_shift=0, max_outstanding_pkts=64) -> FrameParams:
     import socket
-    import struct
+    from .frame_wire import ip_be
     fp = FrameParams()
     fp.dst_mac[:] = list(dst_mac)
     fp.src_mac[:] = list(src_mac)
-    fp.src_ip_be = struct.unpack("<I", socket.inet_aton(src_ip))[0]
-    fp.dst_ip_be = struct.unpack("<I", socket.inet_aton(dst_ip))[0]
+    fp.src_ip_be = ip_be(src_ip)
+    fp.dst_ip_be = ip_be(dst_ip)
     fp.src_port_be = socket.htons(src_port)
     fp.dst_port_be = socket.htons(dst_port)
     fp.job_id = job_id
@@ -86,20 +86,19 @@ class FrameSwitchParams(ctypes.Structure):
 def frame_switch_params(workers, num_slots: int, packet_numel: int = 256, switch_mac=b"\x02\x00\x00\x00\x00\x01",
                         switch_ip="10.0.0.253") -> FrameSwitchParams:
     """`workers`: a (mac bytes, dotted IPv4 string) pair per worker, in worker-id order."""
-    import socket
-    import struct
+    from .frame_wire import ip_be
     workers = list(workers)
     if len(workers) > MAX_FRAME_SWITCH_WORKERS:
         raise ValueError(f"at most {MAX_FRAME_SWITCH_WORKERS} workers (worker_bitmap_t is 32 bits)")
     sp = FrameSwitchParams()
     sp.switch_mac[:] = list(switch_mac)
-    sp.switch_ip_be = struct.unpack("<I", socket.inet_aton(switch_ip))[0]
+    sp.switch_ip_be = ip_be(switch_ip)
     sp.num_workers = len(workers)
     sp.num_slots = num_slots
     sp.packet_numel = packet_numel
     for i, (mac, ip) in enumerate(workers):
         sp.workers[i].mac[:] = list(mac)
-        sp.workers[i].ip_be = struct.unpack("<I", socket.inet_aton(ip))[0]
+        sp.workers[i].ip_be = ip_be(ip)
     return sp
 
 

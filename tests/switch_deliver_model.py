@@ -12,6 +12,7 @@ copy arrives.
 import numpy as np
 
 import switch_frames_model as M
+from switchml_amd import frame_wire as FW
 
 DELIVERED, DROPPED, OVERFLOW, UNROUTABLE = range(4)
 
@@ -23,16 +24,8 @@ LOSSY = dict(W=3, N=40, mop=8, P=64, q=0.1, ring_frames=16 * 40)
 
 
 def worker_checksum(model, u):
-    """The IPv4 header checksum of a result frame to worker u: the header
-    SwitchModel.result() builds, through its ipv4_checksum."""
-    n = M.frame_bytes(model.P)
-    h = np.zeros(20, dtype=np.uint8)
-    h[0], h[1] = 0x45, 0x00
-    h[2:4] = [(n - 14) >> 8, (n - 14) & 0xff]
-    h[8], h[9] = 64, 17
-    h[12:16] = list(model.switch_ip)
-    h[16:20] = list(model.workers[u][1])
-    return M.ipv4_checksum(h)
+    """The IPv4 header checksum of a result frame to worker u."""
+    return FW.result_ipv4_checksum(model.P, model.switch_ip, model.workers[u][1])
 
 
 def copy_for(model, r, u, ck=None):
@@ -40,17 +33,16 @@ def copy_for(model, r, u, ck=None):
     worker_checksum(model, u), where the caller has it at hand)."""
     mac, ip = model.workers[u]
     c = np.array(r, dtype=np.uint8, copy=True)
-    ck = worker_checksum(model, u) if ck is None else ck
-    c[0:6] = list(mac)
-    c[24:26] = [ck >> 8, ck & 0xff]
-    c[30:34] = list(ip)
+    FW.put(c, FW.DST_MAC, mac)
+    FW.put(c, FW.IP_CHECKSUM, worker_checksum(model, u) if ck is None else ck)
+    FW.put(c, FW.DST_IP, ip)
     return c
 
 
 def asker(model, r):
     """The worker a RETRANSMIT answer r is addressed to (its destination
     address, first table match), or None."""
-    dst = bytes(r[30:34])
+    dst = FW.get(r, FW.DST_IP)
     return next((u for u, (_, ip) in enumerate(model.workers) if ip == dst), None)
 
 
@@ -108,7 +100,7 @@ def gather(sets, set_idx, frame_idx):
 
 
 def pkt_id(f):
-    return int(np.asarray(f[44:48]).copy().view("<u4")[0])
+    return FW.get(f, FW.PKT_ID)
 
 
 # ------------------------------------------------------------ the closed loop

@@ -10,21 +10,13 @@ handles the set of the pair's lowest-index frame, the pair's frames of the
 other set are DEFERRED — by filtering the call's frames before the model sees
 them.  Payloads and exponent bytes are opaque bytes to all of it.
 """
-import socket
-import struct
-
 import numpy as np
 
+from switchml_amd import frame_wire as FW
+from switchml_amd.frame_wire import (SWITCH_IP, SWITCH_MAC, frame_bytes, ip_bytes, ipv4_checksum,
+                                     pool_index, worker_frame)
+
 CONSUMED, BROADCAST, RETRANSMIT, IGNORED, DEFERRED = range(5)
-HEADER = 52
-
-
-def frame_bytes(P):
-    return HEADER + 4 * P
-
-
-def ip_bytes(ip):
-    return socket.inet_aton(ip)
 
 
 def default_workers(W):
@@ -32,50 +24,17 @@ def default_workers(W):
     return [(bytes([2, 0, 0, 0, 1, w]), f"10.0.1.{w + 1}") for w in range(W)]
 
 
-SWITCH_MAC = bytes([2, 0, 0, 0, 0, 1])
-SWITCH_IP = "10.0.0.253"
-
-
-def pool_index(p, mop, start=0):
-    """PktId2PoolIndex with shift 0: slot p % mop, sets alternate per window."""
-    i = p % (2 * mop)
-    return (start + i) & 0xffff if i < mop else ((start + i - mop) | 0x8000) & 0xffff
-
-
-def worker_frame(P, worker, pkt_id, pool_idx, payload, exps=(0, 0), src_port=4000, dst_port=48879, job=0,
-                 switch_mac=SWITCH_MAC, switch_ip=SWITCH_IP):
-    """A frame as BuildPacket lays it out (the fields a switch reads, and the
-    rest plausible): `worker` = (mac, ip), payload = 4P wire bytes (uint8 array
-    or bytes), exps = the two bytes at 50-51."""
-    n = frame_bytes(P)
-    f = np.zeros(n, dtype=np.uint8)
-    f[0:6] = list(switch_mac)
-    f[6:12] = list(worker[0])
-    f[12:14] = [0x08, 0x00]
-    f[14] = 0x45
-    f[16:18] = [(n - 14) >> 8, (n - 14) & 0xff]
-    f[22], f[23] = 128, 17
-    f[26:30] = list(ip_bytes(worker[1]))
-    f[30:34] = list(ip_bytes(switch_ip))
-    f[34:36] = [src_port >> 8, src_port & 0xff]
-    f[36:38] = [dst_port >> 8, dst_port & 0xff]
-    f[38:40] = [(n - 34) >> 8, (n - 34) & 0xff]
-    f[42] = (1 << 4) + (0 if P < 64 else 1 if P < 128 else 2 if P < 256 else 3)
-    f[43] = job & 0xff
-    f[44:48] = list(struct.pack("<I", pkt_id))
-    f[48:50] = [pool_idx >> 8, pool_idx & 0xff]
-    f[50:52] = [exps[0] & 0xff, exps[1] & 0xff]
-    f[52:] = np.frombuffer(bytes(payload), dtype=np.uint8) if not isinstance(payload, np.ndarray) else payload
-    return f
-
-
-def ipv4_checksum(hdr20):
-    s = 0
-    for i in range(0, 20, 2):
-        s += (int(hdr20[i]) << 8) | int(hdr20[i + 1])
-    while s >> 16:
-        s = (s & 0xffff) + (s >> 16)
-    return ~s & 0xffff
+def window_frames(rng, P, workers, mop, packets):
+    """One frame per (worker, packet), random bytes (per packet, per worker: the
+    payload, then the two exponent bytes), workers interleaved and shuffled."""
+    frames = []
+    for p in packets:
+        for w, worker in enumerate(workers):
+            pay = rng.integers(0, 256, 4 * P, dtype=np.uint8)
+            e = rng.integers(0, 256, 2, dtype=np.uint8)
+            frames.append(worker_frame(P, worker, p, pool_index(p, mop), pay, e, src_port=4000 + w))
+    order = rng.permutation(len(frames))
+    return [frames[i] for i in order]
 
 
 class SwitchModel:
@@ -95,10 +54,10 @@ class SwitchModel:
 
     def parse(self, f):
         """(w, s, v) or None for a frame the switch ignores."""
-        src = bytes(f[26:30])
+        src = FW.get(f, FW.SRC_IP)
         w = next((i for i, (_, ip) in enumerate(self.workers) if ip == src), None)
-        idx = (int(f[48]) << 8) | int(f[49])
-        s, v = idx & 0x3fff, idx >> 15
+        idx = FW.get(f, FW.POOL_INDEX)
+        s, v = FW.pool_slot(idx), FW.pool_set(idx)
         if w is None or s >= self.S:
             return None
         return w, s, v
@@ -118,8 +77,8 @@ class SwitchModel:
             self.count[s][v] = W - 1 if flag == 0 else flag - 1
             if W == 1:
                 flag = 1
-            words = f[52:52 + 4 * self.P].view(">u4").astype(np.uint32)      # ntohl
-            e = f[50:52].view(np.int8)
+            words = FW.payload_words(f, self.P)
+            e = f[FW.EXPS].view(np.int8)
             if before == 0:
                 self.acc[s, v] = words
                 self.exps[s, v] = e
@@ -135,28 +94,21 @@ class SwitchModel:
         return verdict, self.result(f, w, s, v)
 
     def result(self, f, w, s, v):
-        n = frame_bytes(self.P)
         mac, ip = self.workers[w]
-        r = np.zeros(n, dtype=np.uint8)
-        r[0:6] = list(mac)
-        r[6:12] = list(self.switch_mac)
-        r[12:14] = [0x08, 0x00]
-        r[14], r[15] = 0x45, 0x00
-        r[16:18] = [(n - 14) >> 8, (n - 14) & 0xff]
-        r[22], r[23] = 64, 17
-        r[26:30] = list(self.switch_ip)
-        r[30:34] = list(ip)
-        ck = ipv4_checksum(r[14:34])
-        r[24:26] = [ck >> 8, ck & 0xff]
-        r[34:36] = f[36:38]
-        r[36:38] = f[34:36]
-        r[38:40] = [(n - 34) >> 8, (n - 34) & 0xff]
-        r[42] = 0x10 | (int(f[42]) & 7)
-        r[43:48] = f[43:48]
-        r[48] = int(f[48]) & ~0x40 & 0xff
-        r[49] = f[49]
-        r[50:52] = self.exps[s, v].view(np.uint8)
-        r[52:] = self.acc[s, v].astype(">u4").view(np.uint8)                  # htonl
+        r = np.zeros(frame_bytes(self.P), dtype=np.uint8)
+        FW.put(r, FW.DST_MAC, mac)
+        FW.put(r, FW.SRC_MAC, self.switch_mac)
+        FW.put(r, FW.ETHERTYPE, b"\x08\x00")
+        FW.put_ipv4_header(r, self.P, 64, self.switch_ip, ip)
+        FW.put(r, FW.IP_CHECKSUM, ipv4_checksum(r[FW.IP_HEADER]))
+        r[FW.SRC_PORT] = f[FW.DST_PORT]
+        r[FW.DST_PORT] = f[FW.SRC_PORT]
+        FW.put(r, FW.UDP_LEN, FW.udp_len(self.P))
+        FW.put(r, FW.JOB_TYPE_SIZE, 0x10 | (FW.get(f, FW.JOB_TYPE_SIZE) & 7))
+        r[FW.span(FW.JOB, FW.PKT_ID)] = f[FW.span(FW.JOB, FW.PKT_ID)]
+        FW.put(r, FW.POOL_INDEX, FW.get(f, FW.POOL_INDEX) & ~FW.POOL_BIT14)
+        r[FW.EXPS] = self.exps[s, v].view(np.uint8)
+        FW.put_payload_words(r, self.P, self.acc[s, v])
         return r
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 
 @pytest.fixture(scope="module")
@@ -292,7 +293,7 @@ def test_frames_and_rdma_validation_without_gpu(sw):
     fp = sw.frame_params()
     buf = (ctypes.c_float * 16)()
     frames = (ctypes.c_uint8 * 8192)()
-    assert sw.frame_bytes(256) == 52 + 1024 and sw.frame_bytes(64) == 52 + 256
+    assert sw.frame_bytes(256) == FW.frame_bytes(256) and sw.frame_bytes(64) == FW.frame_bytes(64)
     # unsupported packet size / stride too small / stride not a multiple of 4
     assert L.sml_quantize_pack_frames(buf, 16, 100, 1, None, 64, ctypes.byref(fp), frames, 4096, None) == sw.SML_ERR_UNSUPPORTED
     assert L.sml_quantize_pack_frames(buf, 16, 256, 1, None, 64, ctypes.byref(fp), frames, 1000, None) == sw.SML_ERR_ALIGNMENT

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 pytestmark = pytest.mark.gpu
 
@@ -214,7 +215,7 @@ def test_frames_tx_axes(sw, cuda, P):
     n, W, bm = size(P), 3, 4
     x = planes(P, W)[0]
     B = O.num_blocks(n, P)
-    nframes, fb = B + min(B, bm), 52 + 4 * P
+    nframes, fb = B + min(B, bm), FW.frame_bytes(P)
     stride = fb + 12
     fp = sw.frame_params(job_id=7, pool_index_start=16, pool_index_shift=3, max_outstanding_pkts=bm)
     ge = np.clip(O.exponents(x, P).astype(np.int32) + 1, -128, 127).astype(np.int8)
@@ -239,7 +240,7 @@ def test_frames_tx_int32_axes(sw, cuda, P):
     import torch
     n = size(P)
     x = int32_data(P, n)
-    B, fb = O.num_blocks(n, P), 52 + 4 * P
+    B, fb = O.num_blocks(n, P), FW.frame_bytes(P)
     stride = fb + 12
     fp = sw.frame_params(job_id=9, pool_index_start=16, pool_index_shift=3, max_outstanding_pkts=32)
     ref = O.build_frames_i32(x, fp, P=P)
@@ -264,7 +265,7 @@ def test_frames_rx_axes(sw, cuda, P):
     fstream, _ = rx_stream(x, P, W, bm, job_id=job, seed=P)
     ref = O.dequantize_frames(fstream, fstream.shape[0], fstream.shape[1], O.RxState(n, P, bm), W, job_id=job)
     xi = int32_data(P + 1, n)
-    B, fb = O.num_blocks(n, P), 52 + 4 * P
+    B, fb = O.num_blocks(n, P), FW.frame_bytes(P)
     istream = int32_stream(O.build_frames_i32(xi, sw.frame_params(job_id=7), P=P), B, fb, seed=P)
     iref = O.unpack_frames_i32(istream, istream.size // fb, fb, O.RxStateI32(n, P), job_id=7)
     assert np.array_equal(iref.out, xi)

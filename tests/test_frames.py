@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 
 def params(**kw):
@@ -31,6 +32,7 @@ def test_oracle_frame_fields():
                 src_ip="10.0.0.1", dst_ip="10.0.0.253", src_port=4000, dst_port=48879)
     x = O.splitmix_normal(1, n)
     f = O.build_frames(x, fp, P=P, num_workers=W, batch_max=8)
+    # Spelled out on purpose, not through frame_wire: the independent statement of the format a module bug cannot hide in.
     fb = 52 + 4 * P
     B = O.num_blocks(n, P)
     b = min(B, 8)
@@ -102,7 +104,8 @@ def _frames_match_oracle(cuda, P, n, where):
     ref = O.build_frames(x, fp, P=P, num_workers=W, batch_max=bm)
     B = O.num_blocks(n, P)
     b = min(B, bm)
-    stride = 52 + 4 * P + 12   # mbuf-like padding between frames; padding bytes untouched
+    fb = FW.frame_bytes(P)
+    stride = fb + 12   # mbuf-like padding between frames; padding bytes untouched
     if where == "device":
         frames = torch.full(((B + b) * stride,), 0xAB, dtype=torch.uint8, device=cuda)
     else:
@@ -110,9 +113,9 @@ def _frames_match_oracle(cuda, P, n, where):
     sw.quantize_pack_frames(torch.from_numpy(x).to(cuda), fp, P, W, batch_max=bm, frames=frames, stride=stride)
     torch.cuda.synchronize()
     got = frames.cpu().numpy().reshape(B + b, stride)
-    exp = ref.reshape(B + b, 52 + 4 * P)
-    assert np.array_equal(got[:, :52 + 4 * P], exp)
-    assert np.all(got[:, 52 + 4 * P:] == 0xAB)
+    exp = ref.reshape(B + b, fb)
+    assert np.array_equal(got[:, :fb], exp)
+    assert np.all(got[:, fb:] == 0xAB)
 
 
 @pytest.mark.gpu
@@ -160,7 +163,8 @@ def test_frames_random_parameters(cuda):
         if glob:
             ge = np.clip(O.exponents(x, P).astype(np.int32) + (seed % 3), -128, 127).astype(np.int8)
         ref = O.build_frames(x, fp, P=P, num_workers=W, batch_max=bm, global_exps=ge)
-        stride = 52 + 4 * P + pad
+        fb = FW.frame_bytes(P)
+        stride = fb + pad
         frames = torch.full(((B + b) * stride,), 0xAB, dtype=torch.uint8)
         frames = frames.pin_memory() if pinned else frames.to(cuda)
         xd = torch.from_numpy(xfull).to(cuda)[off:]
@@ -168,8 +172,8 @@ def test_frames_random_parameters(cuda):
                                 global_exps=None if ge is None else torch.from_numpy(ge).to(cuda))
         torch.cuda.synchronize()
         got = frames.cpu().numpy().reshape(B + b, stride)
-        assert np.array_equal(got[:, :52 + 4 * P], ref.reshape(B + b, 52 + 4 * P)), (n, P, W, bm, off)
-        assert np.all(got[:, 52 + 4 * P:] == 0xAB)
+        assert np.array_equal(got[:, :fb], ref.reshape(B + b, fb)), (n, P, W, bm, off)
+        assert np.all(got[:, fb:] == 0xAB)
     check()
 
 
@@ -212,8 +216,8 @@ def test_rdma_messages(cuda, n):
 @pytest.mark.parametrize("where", ["pinned", "device"])
 def test_per_packet_bursts_into_mbufs_equal_bulk_frames(cuda, where):
     """A DPDK worker that keeps the per-packet PPP calls (BuildPacket by the
-    host, then PreprocessSingle into the mbuf: payload at offset 52, extra
-    info at offset 50 — dpdk_worker_thread_utils.inc:132-134) and runs them in
+    host, then PreprocessSingle into the mbuf: payload behind the header, extra
+    info in the exponent byte, dpdk_worker_thread_utils.inc:132-134) and runs them in
     bursts, interleaved with PostprocessSingle of the returned packets as the
     receive loop does (dpdk_worker_thread.cc:300-345), leaves exactly the
     frames the fused frames kernel writes in bulk: the two entry points agree
@@ -224,14 +228,14 @@ def test_per_packet_bursts_into_mbufs_equal_bulk_frames(cuda, where):
     fp = params(job_id=3, max_outstanding_pkts=bm)
     x = O.splitmix_normal(77, n)
     want = O.build_frames(x, fp, P=P, batch_max=bm)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     b = min(B, bm)
     total = B + b
     # BuildPacket's part: the headers; the PPP's part (exponent byte, payload) blank
     pre = want.reshape(total, fb).copy()
-    pre[:, 50] = 0
-    pre[:, 52:] = 0
+    pre[:, FW.EXP] = 0
+    pre[:, FW.payload(P)] = 0
     frames = torch.from_numpy(pre.reshape(-1).copy())
     frames = frames.to(cuda) if where == "device" else frames.pin_memory()
     base = frames.data_ptr()
@@ -243,8 +247,8 @@ def test_per_packet_bursts_into_mbufs_equal_bulk_frames(cuda, where):
     def burst(ids, pre_call):
         if not ids:
             return
-        bt = sw.packet_burst(xd, out, P, 1, b, recv, ids, [base + p * fb + 52 for p in ids],
-                             [base + p * fb + 50 for p in ids])
+        bt = sw.packet_burst(xd, out, P, 1, b, recv, ids, [base + p * fb + FW.HEADER_BYTES for p in ids],
+                             [base + p * fb + FW.EXP.start for p in ids])
         (sw.preprocess_burst if pre_call else sw.postprocess_burst)(bt, stream)
 
     burst(list(range(b)), True)
@@ -271,18 +275,18 @@ def test_per_packet_int32_bursts_into_mbufs_equal_bulk_frames(cuda):
     fp = params(job_id=6)
     xi = np.random.default_rng(8).integers(-2 ** 31, 2 ** 31, n, dtype=np.int64).astype(np.int32)
     want = O.build_frames_i32(xi, fp, P=P)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     pre = want.reshape(B, fb).copy()
-    pre[:, 52:] = 0
+    pre[:, FW.payload(P)] = 0
     frames = torch.from_numpy(pre.reshape(-1).copy()).pin_memory()
     base = frames.data_ptr()
     xd = torch.from_numpy(xi).to(cuda)
     out = torch.zeros(n, dtype=torch.int32, device=cuda)
     for p0 in range(0, B, sw.MAX_BURST):
         ids = list(range(p0, min(p0 + sw.MAX_BURST, B)))
-        bt = sw.packet_burst(xd, out, P, 1, 0, None, ids, [base + p * fb + 52 for p in ids],
-                             [base + p * fb + 50 for p in ids])
+        bt = sw.packet_burst(xd, out, P, 1, 0, None, ids, [base + p * fb + FW.HEADER_BYTES for p in ids],
+                             [base + p * fb + FW.EXP.start for p in ids])
         sw.preprocess_burst(bt)
         sw.postprocess_burst(bt)
     torch.cuda.synchronize()

@@ -14,12 +14,11 @@ oracle — device and pinned frames, every packet size, misaligned slices,
 shuffled streams with duplicates, other jobs' frames and out-of-range
 pkt_ids, split rx calls — and the 16 M-element tx -> rx round trip.
 """
-import struct
-
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 
 def params(**kw):
@@ -41,11 +40,11 @@ def stream(frames, B, fb, seed, dup=0.1, wrong=0.05, bad=3, job=7):
     out = [fr[i].copy() for i in order]
     for _ in range(int(wrong * B) + 1):                                  # another job's frame
         f = fr[rng.integers(B)].copy()
-        f[43] = (job + 1) & 0xFF
+        FW.put(f, FW.JOB, (job + 1) & 0xFF)
         out.insert(int(rng.integers(len(out) + 1)), f)
     for _ in range(bad):                                                 # pkt_id past the slice
         f = fr[rng.integers(B)].copy()
-        f[44:48] = np.frombuffer(struct.pack("<I", B + int(rng.integers(1, 1000))), dtype=np.uint8)
+        FW.put(f, FW.PKT_ID, B + int(rng.integers(1, 1000)))
         out.insert(int(rng.integers(len(out) + 1)), f)
     return np.concatenate(out)
 
@@ -58,17 +57,18 @@ def test_oracle_int32_frames_fields(P, n):
     x = int32_data(P + n, n)
     f = O.build_frames_i32(x, fp, P=P)
     fl = O.build_frames(np.zeros(n, dtype=np.float32), fp, P=P, batch_max=8)    # FLOAT32 frames: same headers
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     assert f.size == B * fb
     for p in range(B):
-        fr = f[p * fb:(p + 1) * fb].tobytes()
-        assert fr[:44] == fl[:44].tobytes()                         # Eth / IPv4 / UDP / job_type_size / job id
-        assert struct.unpack("<I", fr[44:48])[0] == p               # pkt_id, host order, no extra batch
-        assert struct.unpack(">H", fr[48:50])[0] == O.pool_index(p, 64, 10, 8)
-        assert fr[50:52] == b"\0\0"                                 # no exponent for INT32
+        fr = f[p * fb:(p + 1) * fb]
+        constant = FW.span(FW.DST_MAC, FW.JOB)                      # Eth / IPv4 / UDP / job_type_size / job id
+        assert np.array_equal(fr[constant], fl[constant])
+        assert FW.get(fr, FW.PKT_ID) == p                           # host order, no extra batch
+        assert FW.get(fr, FW.POOL_INDEX) == O.pool_index(p, 64, 10, 8)
+        assert FW.get(fr, FW.EXPS) == b"\0\0"                       # no exponent for INT32
         valid = min(P, n - p * P)
-        words = np.frombuffer(fr[52:], dtype=">i4")                 # network order on the wire
+        words = FW.payload_words(fr, P).view(np.int32)              # network order on the wire
         assert np.array_equal(words[:valid].astype(np.int32), x[p * P:p * P + valid])
         assert not words[valid:].any()
 
@@ -78,16 +78,15 @@ def python_rx(stream_bytes, fb, n, P, job, seen, out):
     the INT32 PostprocessSingle)."""
     B = O.num_blocks(n, P)
     acc = dis = 0
-    for i in range(len(stream_bytes) // fb):
-        fr = stream_bytes[i * fb:(i + 1) * fb]
-        pid = struct.unpack("<I", fr[44:48].tobytes())[0]
-        if pid >= B or seen[pid] or fr[43] != (job & 0xFF):
+    rows = stream_bytes[:len(stream_bytes) // fb * fb].reshape(-1, fb)
+    for fr, pid, fr_job in zip(rows, FW.get(rows, FW.PKT_ID).tolist(), FW.get(rows, FW.JOB).tolist()):
+        if pid >= B or seen[pid] or fr_job != (job & 0xFF):
             dis += 1
             continue
         seen[pid] = 1
         acc += 1
         valid = min(P, n - pid * P)
-        out[pid * P:pid * P + valid] = np.frombuffer(fr[52:52 + 4 * valid].tobytes(), dtype=">i4")
+        out[pid * P:pid * P + valid] = FW.payload_words(fr, valid).view(np.int32)
     return acc, dis
 
 
@@ -95,7 +94,7 @@ def python_rx(stream_bytes, fb, n, P, job, seen, out):
 def test_oracle_int32_rx_loop(P, n):
     fp = params(job_id=7, max_outstanding_pkts=16)
     x = int32_data(3 * n, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     s = stream(O.build_frames_i32(x, fp, P=P), B, fb, seed=n)
     half = (len(s) // fb // 2) * fb
@@ -136,7 +135,8 @@ def test_int32_frames_match_oracle(cuda, P, n, where):
     x = int32_data(n + P, n)
     ref = O.build_frames_i32(x, fp, P=P)
     B = O.num_blocks(n, P)
-    stride = 52 + 4 * P + 12          # mbuf-like padding between frames; padding bytes untouched
+    fb = FW.frame_bytes(P)
+    stride = fb + 12                  # mbuf-like padding between frames; padding bytes untouched
     if where == "device":
         frames = torch.full((B * stride,), 0xAB, dtype=torch.uint8, device=cuda)
     else:
@@ -144,10 +144,10 @@ def test_int32_frames_match_oracle(cuda, P, n, where):
     sw.pack_frames_int32(torch.from_numpy(x).to(cuda), fp, P, frames=frames, stride=stride)
     torch.cuda.synchronize()
     got = frames.cpu().numpy().reshape(B, stride)
-    bad = np.argwhere(got[:, :52 + 4 * P] != ref.reshape(B, 52 + 4 * P))
+    bad = np.argwhere(got[:, :fb] != ref.reshape(B, fb))
     assert bad.size == 0, (bad[:8].tolist(), got[bad[0][0], :64].tolist() if bad.size else None,
-                           ref.reshape(B, 52 + 4 * P)[bad[0][0], :64].tolist() if bad.size else None)
-    assert np.all(got[:, 52 + 4 * P:] == 0xAB)
+                           ref.reshape(B, fb)[bad[0][0], :64].tolist() if bad.size else None)
+    assert np.all(got[:, fb:] == 0xAB)
 
 
 @pytest.mark.gpu
@@ -182,7 +182,7 @@ def test_int32_rx_streams_match_oracle(cuda, P, n, where):
     import switchml_amd as sw
     fp = params(job_id=7, max_outstanding_pkts=16)
     x = int32_data(7 * n + P, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     s = stream(O.build_frames_i32(x, fp, P=P), B, fb, seed=n + P)
     nfr = s.size // fb
@@ -209,15 +209,16 @@ def test_int32_rx_streams_match_oracle(cuda, P, n, where):
 
 @pytest.mark.gpu
 def test_int32_rx_ignores_every_other_header_byte(cuda):
-    """As test_frames_rx.py's case of the same name: bytes 0-42 and 48-51 of
-    every frame random (an INT32 slice has no exponent, so byte 50 too), byte
-    43 and the pkt_id kept: output and counts are those of the untouched stream."""
+    """As test_frames_rx.py's case of the same name: everything up to the job
+    type byte, the pool index and both exponent bytes of every frame random (an
+    INT32 slice has no exponent), the job and the pkt_id kept: output and
+    counts are those of the untouched stream."""
     import torch
     import switchml_amd as sw
     P, n = 64, 5 * 64 + 3
     fp = params(job_id=7, max_outstanding_pkts=16)
     x = int32_data(7 * n + P, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     s = stream(O.build_frames_i32(x, fp, P=P), B, fb, seed=n + P)
     nfr = s.size // fb
@@ -226,8 +227,8 @@ def test_int32_rx_ignores_every_other_header_byte(cuda):
     assert np.array_equal(ref.out, x) and ref.counts[1] > 0
     rng = np.random.default_rng(50)
     noisy = s.reshape(nfr, fb).copy()
-    for lo, hi in ((0, 43), (48, 52)):
-        noisy[:, lo:hi] = rng.integers(0, 256, (nfr, hi - lo), dtype=np.uint8)
+    for ignored in (FW.span(FW.DST_MAC, FW.JOB_TYPE_SIZE), FW.span(FW.POOL_INDEX, FW.EXP2)):
+        noisy[:, ignored] = rng.integers(0, 256, (nfr, ignored.stop - ignored.start), dtype=np.uint8)
     for fr in (s, noisy.reshape(-1)):
         rx = sw.RxSliceInt32(n, P, device=cuda)
         rx.reset()
@@ -270,7 +271,7 @@ def altered_copies_stream(frames, B, fb, seed, pairs, max_gap=4096):
     extra = []
     for p in rng.choice(B, min(pairs, B), replace=False):
         alt = fr[p].copy()
-        alt[52:] ^= 0x5A
+        alt[FW.HEADER_BYTES:] ^= 0x5A
         gap = int(rng.integers(1, max_gap + 1)) * (1 if rng.random() < 0.5 else -1)
         extra.append((pos[p] + gap + 0.5 * np.sign(gap), alt))
     items = [(pos[p], fr[p]) for p in range(B)] + extra
@@ -290,7 +291,7 @@ def test_int32_rx_first_copy_wins_over_racing_copies(cuda, P, n, pairs):
     import switchml_amd as sw
     fp = params(job_id=5)
     x = int32_data(P + 17, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     s = altered_copies_stream(O.build_frames_i32(x, fp, P=P), B, fb, seed=P, pairs=pairs)
     nfr = s.size // fb
@@ -320,11 +321,11 @@ def lead_stream(x, fp, P, K, pairs_iters, other_job):
     F pkt_ids and wave 1's tile later, altered copies of the same pkt_ids —
     which wave 1 reaches first.  Returns the stream bytes."""
     F = 1024 // P
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(x.size, P)
     fr = O.build_frames_i32(x, fp, P=P).reshape(B, fb)
     other = fr[0].copy()
-    other[43] = other_job
+    FW.put(other, FW.JOB, other_job)
     tiles = []
     pid = 0
     for _ in range(K):
@@ -335,7 +336,7 @@ def lead_stream(x, fp, P, K, pairs_iters, other_job):
         first = [fr[pid + j] for j in range(F)]
         alt = [f.copy() for f in first]
         for a in alt:
-            a[52:] ^= 0x5A
+            a[FW.HEADER_BYTES:] ^= 0x5A
         tiles += [first, alt, [other] * F, [other] * F]
         pid += F
     assert pid <= B
@@ -364,7 +365,7 @@ def test_int32_rx_racing_copies_smoke(cuda, P):
     n = (K + pairs_iters) * F * P
     fp = params(job_id=5)
     x = int32_data(P, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     s = lead_stream(x, fp, P, K, pairs_iters, other_job=6)
     nfr = s.size // fb
@@ -413,7 +414,7 @@ def test_int32_rx_fixup_rewrites_displaced_claims(cuda, P, overflow):
     n = 40_000 + 7
     fp = params(job_id=4)
     x = int32_data(P + 3, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     frames = O.build_frames_i32(x, fp, P=P)
     rng = np.random.default_rng(P)
@@ -460,7 +461,7 @@ def test_int32_rx_many_calls_keep_earlier_winners(cuda):
     P, n = 256, 300_001
     fp = params(job_id=9)
     x = int32_data(99, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     s = altered_copies_stream(O.build_frames_i32(x, fp, P=P), B, fb, seed=3, pairs=600, max_gap=B)
     nfr = s.size // fb
@@ -532,7 +533,7 @@ def test_int32_rx_random_streams(cuda):
     def check(n, P, job, pairs, wrong, bad, drop, calls, seed):
         rng = np.random.default_rng(seed)
         fp = params(job_id=job)
-        fb = 52 + 4 * P
+        fb = FW.frame_bytes(P)
         B = O.num_blocks(n, P)
         x = int32_data(seed, n)
         if B:
@@ -545,15 +546,15 @@ def test_int32_rx_random_streams(cuda):
         else:
             rows = []
             other = np.zeros(fb, dtype=np.uint8)
-            other[43] = job
+            FW.put(other, FW.JOB, job)
         for _ in range(wrong):
             f = other.copy()
-            f[43] = (job + 1) & 0xFF
+            FW.put(f, FW.JOB, (job + 1) & 0xFF)
             rows.insert(int(rng.integers(len(rows) + 1)), f)
         for _ in range(bad):
             f = other.copy()
-            f[43] = job & 0xFF
-            f[44:48] = np.frombuffer(struct.pack("<I", B + int(rng.integers(0, 5))), dtype=np.uint8)
+            FW.put(f, FW.JOB, job & 0xFF)
+            FW.put(f, FW.PKT_ID, B + int(rng.integers(0, 5)))
             rows.insert(int(rng.integers(len(rows) + 1)), f)
         if not rows:
             return
@@ -599,12 +600,13 @@ def test_int32_frames_random_parameters(cuda):
         full = int32_data(seed, n + off)
         ref = O.build_frames_i32(full[off:], fp, P=P)
         B = O.num_blocks(n, P)
-        stride = 52 + 4 * P + pad
+        fb = FW.frame_bytes(P)
+        stride = fb + pad
         frames = torch.full((B * stride,), 0xAB, dtype=torch.uint8)
         frames = frames.pin_memory() if pinned else frames.to(cuda)
         sw.pack_frames_int32(torch.from_numpy(full).to(cuda)[off:], fp, P, frames=frames, stride=stride)
         torch.cuda.synchronize()
         got = frames.cpu().numpy().reshape(B, stride)
-        assert np.array_equal(got[:, :52 + 4 * P], ref.reshape(B, 52 + 4 * P)), (n, P, off)
-        assert np.all(got[:, 52 + 4 * P:] == 0xAB)
+        assert np.array_equal(got[:, :fb], ref.reshape(B, fb)), (n, P, off)
+        assert np.all(got[:, fb:] == 0xAB)
     check()

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 
 def _params(job_id):
@@ -30,8 +31,8 @@ def _params(job_id):
 def switch_return(sent, stride, P, W):
     """DummyBackend::ProcessPacket on every frame: BE payload words x W (wrap)."""
     f = sent.reshape(-1, stride).copy()
-    pl = f[:, 52:52 + 4 * P].copy().view(">u4").astype(np.uint64)
-    f[:, 52:52 + 4 * P] = ((pl * W) & 0xFFFFFFFF).astype(">u4").view(np.uint8)
+    pl = FW.payload_words(f, P).astype(np.uint64)
+    FW.put_payload_words(f, P, (pl * W) & 0xFFFFFFFF)
     return f
 
 
@@ -39,7 +40,7 @@ def rx_stream(x, P, W, batch_max, job_id, seed, n_dups=3, n_wrong=2, bad_pid=Tru
     """(frames [F, stride] uint8 in rx order, number of frames that must be discarded).
     shuffle=False keeps the switch's return order (frame f carries pkt_id f)
     before the anomalies are inserted."""
-    stride = 52 + 4 * P
+    stride = FW.frame_bytes(P)
     sent = O.build_frames(x, _params(job_id), P=P, num_workers=W, batch_max=batch_max)
     ret = switch_return(sent, stride, P, W)
     B = O.num_blocks(x.size, P)
@@ -56,19 +57,19 @@ def rx_stream(x, P, W, batch_max, job_id, seed, n_dups=3, n_wrong=2, bad_pid=Tru
     for _ in range(n_dups):                        # a later garbage copy of a received packet
         pos = int(rng.integers(0, len(rows)))
         dup = rows[pos].copy()
-        dup[50] ^= 0x5A
-        dup[52:] = rng.integers(0, 256, dup.size - 52, dtype=np.uint8)
+        dup[FW.EXP] ^= 0x5A
+        dup[FW.payload(P)] = rng.integers(0, 256, 4 * P, dtype=np.uint8)
         rows.insert(int(rng.integers(pos + 1, len(rows) + 1)), dup)
         discard += 1
     for _ in range(n_wrong):                       # another job's frame, anywhere
         src = rows[int(rng.integers(0, len(rows)))].copy()
-        src[43] = (job_id + 1) & 0xFF
-        src[52:] = 0xEE
+        FW.put(src, FW.JOB, (job_id + 1) & 0xFF)
+        src[FW.payload(P)] = 0xEE
         rows.insert(int(rng.integers(0, len(rows) + 1)), src)
         discard += 1
     if bad_pid:
         bad = rows[0].copy()
-        bad[44:48] = np.frombuffer(np.uint32(B + b + 5).tobytes(), dtype=np.uint8)
+        FW.put(bad, FW.PKT_ID, B + b + 5)
         rows.insert(int(rng.integers(0, len(rows) + 1)), bad)
         discard += 1
     return np.stack(rows), discard
@@ -149,9 +150,10 @@ def test_rx_frames_match_oracle(cuda, P, n, W, bm, where):
 def test_rx_ignores_every_other_header_byte(cuda):
     """The oracle's frames are zero in most header bytes the receive side must
     not read, so a mask reaching into a neighbouring byte would pass on them.
-    Here bytes 0-42, 48-49 and 51 of every frame are random (byte 43, the job,
-    the pkt_id at 44-47 and the exponent byte 50 are kept): output, exponents
-    and counts are those of the untouched stream."""
+    Here everything up to the job type byte, the pool index and the second
+    exponent of every frame are random (the job, the pkt_id and the exponent
+    byte are kept): output, exponents and counts are those of the untouched
+    stream."""
     import torch
     import switchml_amd as sw
     P, n, W, bm, job = 64, 5 * 64 + 3, 2, 2, 0x3C
@@ -159,8 +161,8 @@ def test_rx_ignores_every_other_header_byte(cuda):
     frames, disc = rx_stream(x, P, W, bm, job_id=job, seed=n + P)
     rng = np.random.default_rng(43)
     noisy = frames.copy()
-    for lo, hi in ((0, 43), (48, 50), (51, 52)):
-        noisy[:, lo:hi] = rng.integers(0, 256, (frames.shape[0], hi - lo), dtype=np.uint8)
+    for ignored in (FW.span(FW.DST_MAC, FW.JOB_TYPE_SIZE), FW.POOL_INDEX, FW.EXP2):
+        noisy[:, ignored] = rng.integers(0, 256, (frames.shape[0], ignored.stop - ignored.start), dtype=np.uint8)
     ref = O.dequantize_frames(frames, frames.shape[0], frames.shape[1], O.RxState(n, P, bm), W, job_id=job)
     assert ref.counts[1] == disc
     for fr in (frames, noisy):
@@ -171,7 +173,7 @@ def test_rx_ignores_every_other_header_byte(cuda):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("P,pad", [(256, 12), (64, 2048 - 52 - 4 * 64), (1024, 4)])
+@pytest.mark.parametrize("P,pad", [(256, 12), (64, 2048 - FW.frame_bytes(64)), (1024, 4)])
 def test_rx_frames_padded_stride(cuda, P, pad):
     """Frames at an mbuf-like stride (frame bytes + padding, e.g. a 2 KiB data
     room): padding bytes are ignored, results equal the oracle's loop."""
@@ -225,10 +227,10 @@ def test_frames_tx_rx_round_trip_equals_fused_loopback(cuda, W):
     stride = sw.frame_bytes(P)
     fr = sw.quantize_pack_frames(x, sw.frame_params(job_id=4), packet_numel=P, num_workers=W, batch_max=bm)
     F = fr.numel() // stride
-    v = fr.view(F, stride)[:, 52:52 + 4 * P].contiguous().view(torch.int32)
+    v = fr.view(F, stride)[:, FW.payload(P)].contiguous().view(torch.int32)
     v = (v.view(torch.uint8).view(F, P, 4).flip(-1).contiguous().view(torch.int32) * W)   # ntohl, x W (wraps)
     v = v.view(torch.uint8).view(F, P, 4).flip(-1).contiguous().view(F, 4 * P)           # htonl
-    fr.view(F, stride)[:, 52:52 + 4 * P] = v
+    fr.view(F, stride)[:, FW.payload(P)] = v
     ref = sw.roundtrip_loopback(x, P, W)
     # both output store policies of the apply pass (non-temporal from the
     # threshold on — 0 here — or default): the same bytes
@@ -336,16 +338,16 @@ def test_rx_in_order_then_miss(cuda, P, kind):
         fr = fr.copy()
         i = fr.shape[0] * 2 // 3
         if kind == "wrong_job":
-            fr[i, 43] ^= 0x01
+            fr[i, FW.JOB] ^= 0x01
         elif kind == "dup_of_earlier_call":         # a copy of frame 3 (first call) inside the second call
             fr = np.concatenate([fr[:i], fr[3:4], fr[i:]])
         elif kind == "swap":
             fr[[i, i + 1]] = fr[[i + 1, i]]
         elif kind == "bad_pid":
-            fr[i, 44:48] = np.frombuffer(np.uint32(0xFFFFFF00).tobytes(), dtype=np.uint8)
+            FW.put(fr[i], FW.PKT_ID, 0xFFFFFF00)
         else:                                     # garbage second copy of frame i, right after it
             d = fr[i].copy()
-            d[52:] ^= 0xA5
+            d[FW.payload(P)] ^= 0xA5
             fr = np.concatenate([fr[:i + 1], d[None], fr[i + 1:]])
         return fr
     B = O.num_blocks(n, P)
@@ -381,9 +383,9 @@ def test_rx_in_order_random(cuda):
                     j = int(rng.integers(0, i + 1))
                     fr = np.concatenate([fr[:i + 1], fr[j:j + 1], fr[i + 1:]])
                 elif kind == "job":
-                    fr[i, 43] ^= 0x80
+                    fr[i, FW.JOB] ^= 0x80
                 elif kind == "pid":
-                    fr[i, 44:48] = np.frombuffer(np.uint32(int(rng.integers(0, 2 ** 32))).tobytes(), dtype=np.uint8)
+                    FW.put(fr[i], FW.PKT_ID, int(rng.integers(0, 2 ** 32)))
             return fr
         B = O.num_blocks(n, P)
         F = B + min(B, bm)

@@ -5,6 +5,8 @@ import ctypes
 
 import pytest
 
+from switchml_amd import frame_wire as FW
+
 F32, I32, F16, BF16 = 0, 1, 2, 3
 TYPED = ("sml_quantize_pack_frames_typed", "sml_dequantize_frames_typed")
 
@@ -37,7 +39,7 @@ def test_tx_typed_validation_without_gpu(sw, dt):
     L, m = sw.lib(), Mem()
     prm = sw.frame_params(job_id=3)
     n, P, W, bm = 16, 256, 2, 4
-    stride = 52 + 4 * P
+    stride = FW.frame_bytes(P)
 
     def call(buf, dt, n, P, W, bm, frames=m.frames, stride=stride, prm=prm):
         return L.sml_quantize_pack_frames_typed(buf, dt, n, P, W, None, bm, ctypes.byref(prm) if prm else None,
@@ -73,7 +75,7 @@ def test_tx_typed_validation_without_gpu(sw, dt):
 def test_rx_typed_validation_without_gpu(sw, dt):
     L, m = sw.lib(), Mem()
     n, P, W, bm, F = 16, 256, 2, 4, 2
-    stride = 52 + 4 * P
+    stride = FW.frame_bytes(P)
 
     def call(out, dt, F, P, W, bm, frames=m.frames, stride=stride, state=m.state, exps=m.exps, counts=m.counts, n=n):
         return L.sml_dequantize_frames_typed(frames, F, stride, n, P, W, bm, 7, exps, state, out, dt, counts, None)

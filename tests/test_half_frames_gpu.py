@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 from test_frames import rdma_imm_reference
 from test_frames_rx import rx_stream, switch_return
 from test_half_gpu import assert_half_equal, bits_of, from_bits, make, narrow, tdtype, x32_of
@@ -60,13 +61,13 @@ def slice_of(kind, T, P, n):
 
 @functools.lru_cache(maxsize=None)
 def expected_frames(kind, T, P, n, W, bm, glob):
-    """The oracle's frames of the widened slice, [B + b, 52 + 4P]; glob: global
+    """The oracle's frames of the widened slice, [B + b, frame bytes]; glob: global
     exponents one above the slice's own, returned with them."""
     _, x32 = slice_of(kind, T, P, n)
     ge = None
     if glob:
         ge = np.clip(O.exponents(x32, P).astype(np.int32) + 1, -128, 127).astype(np.int8)
-    fr = O.build_frames(x32, params(), P=P, num_workers=W, batch_max=bm, global_exps=ge).reshape(-1, 52 + 4 * P)
+    fr = O.build_frames(x32, params(), P=P, num_workers=W, batch_max=bm, global_exps=ge).reshape(-1, FW.frame_bytes(P))
     fr.setflags(write=False)
     return fr, ge
 
@@ -179,8 +180,8 @@ def test_rx_blocks_without_a_payload_frame_keep_their_bytes(cuda, P, n, W, bm, T
     B = O.num_blocks(n, P)
     b = min(B, bm)
     lost = (0, B - 1)                                        # the first block and the (partial) last one
-    pid = frames[:, 44:48].copy().view(np.uint32)[:, 0]
-    mine = frames[:, 43] == JOB
+    pid = FW.get(frames, FW.PKT_ID)
+    mine = FW.get(frames, FW.JOB) == JOB
     keep = ~(mine & np.isin(pid, [k + b for k in lost]))
     frames = np.ascontiguousarray(frames[keep])
     out, whole, exps, cnt, cuts = run_rx(cuda, frames, T, P, n, W, bm, 1, 1)
@@ -232,7 +233,7 @@ def test_typed_entry_points_with_float32_are_the_untyped_ones(cuda):
     xd = torch.from_numpy(x32).to(cuda)
     prm = params()
     B = O.num_blocks(n, P)
-    F, stride = B + min(B, bm), 52 + 4 * P
+    F, stride = B + min(B, bm), FW.frame_bytes(P)
     st = ctypes.c_void_p(torch.cuda.current_stream(cuda).cuda_stream)
     fr = [torch.full((F * stride,), SENT8, dtype=torch.uint8, device=cuda) for _ in range(2)]
     assert L.sml_quantize_pack_frames(xd.data_ptr(), n, P, W, None, bm, ctypes.byref(prm), fr[0].data_ptr(), stride,

@@ -10,6 +10,7 @@ import pytest
 
 import switch_deliver_model as D
 import switch_frames_model as M
+from switchml_amd import frame_wire as FW
 
 
 @pytest.fixture(scope="module")
@@ -47,7 +48,7 @@ def test_broadcast_copy_is_the_switch_models_result(W):
     for u in range(W):
         want = model.result(frames[last], u, 2, 1)
         assert np.array_equal(appended[u][0], want), u
-        assert M.ipv4_checksum(appended[u][0][14:34]) == 0
+        assert M.ipv4_checksum(appended[u][0][FW.IP_HEADER]) == 0
     assert np.array_equal(appended[last][0], results[last])           # the addressee's copy: byte for byte
 
 
@@ -65,7 +66,7 @@ def test_retransmit_reaches_only_its_asker():
     assert appended[1][1] is results[3]                               # unchanged
     # an answer to nobody the table knows
     stray = results[3].copy()
-    stray[30:34] = [10, 9, 9, 9]
+    stray[FW.DST_IP] = [10, 9, 9, 9]
     appended, counts, fill = D.deliver(model, frames[3:], verdicts[3:], {0: stray}, None, [0] * W, 8)
     assert fill == [0, 0, 0] and counts == [0, 0, 0, 1]
 
@@ -97,7 +98,7 @@ def test_ring_order():
         want = [i for i in range(n) if not (drop[i] >> u) & 1 and
                 (verdicts[i] == M.BROADCAST or (verdicts[i] == M.RETRANSMIT and D.asker(model, results[i]) == u))]
         assert [D.pkt_id(f) for f in appended[u]] == want
-        assert all(bytes(f[0:6]) == model.workers[u][0] and bytes(f[30:34]) == model.workers[u][1]
+        assert all(FW.get(f, FW.DST_MAC) == model.workers[u][0] and FW.get(f, FW.DST_IP) == model.workers[u][1]
                    for f in appended[u])
         total += len(want)
     copies = sum(W if v == M.BROADCAST else 1 for v in verdicts if v in (M.BROADCAST, M.RETRANSMIT))
@@ -146,7 +147,7 @@ def test_lossy_loop_finishes_on_the_model(seed):
     for u in range(c["W"]):
         got = {}
         for f in switch.rings[u]:
-            got.setdefault(D.pkt_id(f), f[52:].copy().view(">u4").astype(np.uint32))
+            got.setdefault(D.pkt_id(f), FW.payload_words(f, c["P"]))
         assert sorted(got) == list(range(c["N"]))
         assert all(np.array_equal(got[p], want[p * c["P"]:(p + 1) * c["P"]]) for p in got)
 
@@ -164,7 +165,7 @@ def test_deliver_argument_checks_without_gpu(sw):
         sp.num_workers = W
         return ctypes.byref(sp)
 
-    fb = 52 + 256
+    fb = FW.frame_bytes(64)
     out, vd, dr, rg, rc, cnt, sc = vp(4096), vp(8192), vp(12288), vp(16384), vp(32768), vp(65536), vp(131072)
     good = dict(prm=None, out=out, n=1, ostr=fb, vd=vd, dr=dr, rg=rg, rb=4 * fb, rf=4, rx=fb, rc=rc, cnt=cnt, sc=sc)
 
@@ -214,7 +215,7 @@ def test_gather_argument_checks_without_gpu(sw):
     vp = ctypes.c_void_p
     f = L.sml_frame_gather
     INV, UNS, ALN, OK = sw.SML_ERR_INVALID_ARG, sw.SML_ERR_UNSUPPORTED, sw.SML_ERR_ALIGNMENT, sw.SML_OK
-    fb = 52 + 256
+    fb = FW.frame_bytes(64)
 
     def sets(*ptrs):
         return (vp * len(ptrs))(*ptrs)

@@ -11,6 +11,7 @@ import pytest
 import switch_deliver_model as D
 import switch_frames_model as M
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 pytestmark = pytest.mark.gpu
 
@@ -90,12 +91,7 @@ def to_device(results, n, fb, out_stride=None, fill=0xC3):
 
 def window(rng, model, mop, packets):
     """One frame per (worker, packet), shuffled; through the model: (frames, verdicts, results)."""
-    P, W = model.P, model.W
-    workers = M.default_workers(W)
-    frames = [M.worker_frame(P, workers[w], p, M.pool_index(p, mop), rng.integers(0, 256, 4 * P, dtype=np.uint8),
-                             rng.integers(0, 256, 2, dtype=np.uint8), src_port=4000 + w)
-              for p in packets for w in range(W)]
-    frames = [frames[i] for i in rng.permutation(len(frames))]
+    frames = M.window_frames(rng, model.P, M.default_workers(model.W), mop, packets)
     verdicts, results, _ = M.model_call(model, frames)
     return frames, verdicts, results
 
@@ -109,9 +105,9 @@ def synthetic_host(rng, model, n):
     buf = rng.integers(0, 256, (n, fb), dtype=np.uint8)
     to = rng.integers(0, model.W, n)
     ips = np.array([list(ip) for _, ip in model.workers], dtype=np.uint8)
-    buf[:, 30:34] = ips[to]
-    buf[rng.random(n) < 1 / 16, 30:34] = [10, 9, 9, 9]
-    buf[:, 44:48] = np.arange(n, dtype="<u4").view(np.uint8).reshape(n, 4)
+    buf[:, FW.DST_IP] = ips[to]
+    buf[rng.random(n) < 1 / 16, FW.DST_IP] = [10, 9, 9, 9]
+    FW.put(buf, FW.PKT_ID, np.arange(n))
     results = {int(i): buf[i] for i in np.flatnonzero((verdicts == M.BROADCAST) | (verdicts == M.RETRANSMIT))}
     return verdicts, results, buf
 
@@ -147,12 +143,8 @@ def test_replication(sw, P, W):
         mac, ip = model.workers[u]
         for k in range(mop):
             f = got[u, k]
-            assert bytes(f[0:6]) == mac and bytes(f[30:34]) == ip
-            words = f[14:34].copy().view(">u2").astype(np.uint32)
-            s = int(words.sum())
-            while s >> 16:
-                s = (s & 0xffff) + (s >> 16)
-            assert s == 0xffff
+            assert FW.get(f, FW.DST_MAC) == mac and FW.get(f, FW.DST_IP) == ip
+            assert FW.ipv4_checksum(f[FW.IP_HEADER]) == 0
         assert sorted(D.pkt_id(got[u, k]) for k in range(mop)) == list(range(mop))
 
 
@@ -325,7 +317,7 @@ def check_addresses(rings, ring_count, workers):
     got = rings.cpu().numpy()
     for u, (mac, ip) in enumerate(workers):
         for k in range(int(ring_count[u])):
-            assert bytes(got[u, k, 0:6]) == mac and bytes(got[u, k, 30:34]) == M.ip_bytes(ip), (u, k)
+            assert FW.get(got[u, k], FW.DST_MAC) == mac and FW.get(got[u, k], FW.DST_IP) == M.ip_bytes(ip), (u, k)
         assert np.all(got[u, int(ring_count[u]):] == SENTINEL)
 
 
@@ -351,7 +343,7 @@ def test_closed_loop_float(sw, dtype):
     # a window's results are in completion order: pkt_id p's exponent from whichever position holds it
     r0 = rings[0].cpu().numpy()
     by_pkt = {D.pkt_id(f): f for f in r0}
-    gexp_host = np.array([by_pkt[p][50] for p in range(B)], dtype=np.uint8).view(np.int8)
+    gexp_host = np.array([FW.get(by_pkt[p], FW.EXP) for p in range(B)], dtype=np.uint8).view(np.int8)
     assert np.array_equal(gexp_host, want_exps)
     gexp = torch.from_numpy(gexp_host).cuda()
     glob = [sw.quantize_pack_frames(xd[w], prm[w], P, W, batch_max=mop, global_exps=gexp) for w in range(W)]
@@ -420,12 +412,12 @@ class GpuSwitch:
         verdicts = verdict.cpu().numpy()
         fill = ring_count.tolist()
         # the workers' view: the pkt_id field of the new ring entries
-        ids = self.rings[:, :, 44:48].cpu().numpy().copy().view("<u4")[:, :, 0]
+        got = self.rings.cpu().numpy()
+        ids = FW.get(got, FW.PKT_ID)
         new_ids = [[int(p) for p in ids[u, self.seen[u]:fill[u]]] for u in range(self.W)]
         want_v, want_fill, want_ids = self.model.call(batch, drop)
         assert verdicts.tolist() == want_v.tolist()
         assert fill == want_fill and new_ids == want_ids
-        got = self.rings.cpu().numpy()
         for u in range(self.W):
             for k in range(self.seen[u], fill[u]):
                 assert np.array_equal(got[u, k], self.model.rings[u][k]), (u, k)

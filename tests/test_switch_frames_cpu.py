@@ -9,6 +9,7 @@ import pytest
 
 import switch_frames_model as M
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 
 @pytest.fixture(scope="module")
@@ -48,15 +49,15 @@ def test_lossless_stream_equals_the_plane_switch(W, N, mop, P):
         assert not np.any(verdicts == M.IGNORED)
         for i, r in results.items():
             assert verdicts[i] == M.BROADCAST            # nothing is lost: nobody asks twice
-            p = int(np.frombuffer(bytes(r[44:48]), dtype="<u4")[0])
+            p = FW.get(r, FW.PKT_ID)
             assert p not in seen
             seen[p] = r
     assert sorted(seen) == list(range(N))
     for p, r in seen.items():
         words, e = oracle_result(payloads, exps, p)
-        assert np.array_equal(r[52:], words), p
-        assert np.array_equal(r[50:52], e), p
-        assert (int(r[48]) << 8 | int(r[49])) == M.pool_index(p, mop) & ~0x4000
+        assert np.array_equal(r[FW.HEADER_BYTES:], words), p
+        assert np.array_equal(r[FW.EXPS], e), p
+        assert FW.get(r, FW.POOL_INDEX) == M.pool_index(p, mop) & ~FW.POOL_BIT14
 
 
 def test_single_worker_echoes_the_payload():
@@ -66,14 +67,15 @@ def test_single_worker_echoes_the_payload():
     for frames, verdicts, results in run_calls(model, calls):
         assert np.all(verdicts == M.BROADCAST)
         for i, r in results.items():
-            assert np.array_equal(r[50:], frames[i][50:])
+            assert np.array_equal(r[FW.EXP.start:], frames[i][FW.EXP.start:])
     # a duplicate is answered, with the same words
     f = M.worker_frame(P, M.default_workers(1)[0], 4, M.pool_index(4, mop), payloads[0, 4], exps[0, 4])
     verdict, r = model.frame(f)
-    assert verdict == M.RETRANSMIT and np.array_equal(r[50:], f[50:])
+    assert verdict == M.RETRANSMIT and np.array_equal(r[FW.EXP.start:], f[FW.EXP.start:])
 
 
 def test_result_header_fields():
+    # Spelled out on purpose, not through frame_wire: the independent statement of the format a module bug cannot hide in.
     P, W = 64, 2
     workers = M.default_workers(W)
     model = M.SwitchModel(workers, 4, P)
@@ -149,7 +151,7 @@ def test_argument_checks_without_gpu(sw):
         return ctypes.byref(sp)
 
     fr, st, out, vd, cnt = vp(4096), vp(8192), vp(16384), vp(32768), vp(65536)
-    fb = 52 + 256
+    fb = FW.frame_bytes(64)
     # null
     assert f(None, fr, 1, fb, st, out, fb, vd, cnt, None) == INV
     assert f(params(W=0), fr, 1, fb, st, out, fb, vd, cnt, None) == INV

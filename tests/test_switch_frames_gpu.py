@@ -7,6 +7,7 @@ import pytest
 
 import switch_frames_model as M
 from oracle import oracle as O
+from switchml_amd import frame_wire as FW
 
 pytestmark = pytest.mark.gpu
 
@@ -76,24 +77,11 @@ class Pair:
         return verdicts, results
 
 
-def window_frames(rng, pair, mop, packets, payloads=None, exps=None):
-    """One frame per (worker, packet), random bytes, workers interleaved and shuffled."""
-    P, W = pair.P, pair.W
-    frames = []
-    for p in packets:
-        for w in range(W):
-            pay = rng.integers(0, 256, 4 * P, dtype=np.uint8) if payloads is None else payloads[w][p]
-            e = rng.integers(0, 256, 2, dtype=np.uint8) if exps is None else exps[w][p]
-            frames.append(M.worker_frame(P, pair.workers[w], p, M.pool_index(p, mop), pay, e, src_port=4000 + w))
-    order = rng.permutation(len(frames))
-    return [frames[i] for i in order]
-
-
 def aggregate(frames_of_packet):
-    """Wire bytes 50.. of W frames' aggregate, by the oracle's plane-level switch."""
-    words = O.switch_payload([f[52:].copy().view(np.uint32) for f in frames_of_packet])
-    e0 = O.switch_exps([f[50:51].copy().view(np.int8) for f in frames_of_packet])
-    e1 = O.switch_exps([f[51:52].copy().view(np.int8) for f in frames_of_packet])
+    """The wire bytes from the exponents on of W frames' aggregate, by the oracle's plane-level switch."""
+    words = O.switch_payload([f[FW.HEADER_BYTES:].copy().view(np.uint32) for f in frames_of_packet])
+    e0 = O.switch_exps([f[FW.EXP].copy().view(np.int8) for f in frames_of_packet])
+    e1 = O.switch_exps([f[FW.EXP2].copy().view(np.int8) for f in frames_of_packet])
     return np.concatenate([e0.view(np.uint8), e1.view(np.uint8), words.view(np.uint8)])
 
 
@@ -106,37 +94,40 @@ def test_slot_reuse_overwrites(sw):
     pair = Pair(sw, 3, mop, 64)
     for k in range(3):
         packets = list(range(k * mop, min((k + 1) * mop, 2 * mop + 3)))
-        frames = window_frames(rng, pair, mop, packets)
+        frames = M.window_frames(rng, pair.P, pair.workers, mop, packets)
         verdicts, results = pair.check(frames)
         assert int(np.sum(verdicts == M.BROADCAST)) == len(packets)
         for i, r in results.items():
-            p = int(r[44:48].copy().view("<u4")[0])
-            same = [f for f in frames if int(f[44:48].copy().view("<u4")[0]) == p]
-            assert np.array_equal(r[50:], aggregate(same)), p
+            p = FW.get(r, FW.PKT_ID)
+            same = [f for f in frames if FW.get(f, FW.PKT_ID) == p]
+            assert np.array_equal(r[FW.EXP.start:], aggregate(same)), p
 
 
 def test_bytes_the_switch_ignores_are_random(sw):
     """W = 2, S = mop = 4, P = 64, one window of 8 frames, then the same 8 again
     as retransmissions.  worker_frame() leaves most of the header zero, which
     a mask reaching into a neighbouring byte would not notice; here every byte
-    the switch does not read is random per frame (bytes 0-25, 38-43, the tsi at
-    44-47, bit 14 of the pool index), byte 42's high bits included, and the
-    model builds its results from the same bytes."""
+    the switch does not read is random per frame (the destination MAC to the
+    header checksum, the UDP length to the job, the tsi, bit 14 of the pool
+    index), the job type byte's high bits included, and the model builds its
+    results from the same bytes."""
     rng = np.random.default_rng(14)
     mop = 4
     pair = Pair(sw, 2, mop, 64)
-    frames = window_frames(rng, pair, mop, range(mop))
+    frames = M.window_frames(rng, pair.P, pair.workers, mop, range(mop))
     assert len(frames) == 8
     for f in frames:
-        for lo, hi in ((0, 26), (38, 48)):
-            f[lo:hi] = rng.integers(0, 256, hi - lo, dtype=np.uint8)
-        f[48] |= int(rng.integers(0, 2)) << 6
-    assert any(f[42] & 0xe8 for f in frames) and any(f[48] & 0x40 for f in frames)
+        for ignored in (FW.span(FW.DST_MAC, FW.IP_CHECKSUM), FW.span(FW.UDP_LEN, FW.PKT_ID)):
+            f[ignored] = rng.integers(0, 256, ignored.stop - ignored.start, dtype=np.uint8)
+        FW.put(f, FW.POOL_INDEX, FW.get(f, FW.POOL_INDEX) | int(rng.integers(0, 2)) * FW.POOL_BIT14)
+    assert any(FW.get(f, FW.JOB_TYPE_SIZE) & 0xe8 for f in frames)
+    assert any(FW.get(f, FW.POOL_INDEX) & FW.POOL_BIT14 for f in frames)
     verdicts, results = pair.check(frames)
     assert int(np.sum(verdicts == M.BROADCAST)) == mop and int(np.sum(verdicts == M.CONSUMED)) == mop
     for i, r in results.items():
-        assert r[42] == 0x10 | (int(frames[i][42]) & 7) and not r[48] & 0x40
-        assert bytes(r[43:48]) == bytes(frames[i][43:48])
+        assert FW.get(r, FW.JOB_TYPE_SIZE) == 0x10 | (FW.get(frames[i], FW.JOB_TYPE_SIZE) & 7)
+        assert not FW.get(r, FW.POOL_INDEX) & FW.POOL_BIT14
+        assert FW.get(r, FW.span(FW.JOB, FW.PKT_ID)) == FW.get(frames[i], FW.span(FW.JOB, FW.PKT_ID))
     verdicts, results = pair.check(frames)
     assert np.all(verdicts == M.RETRANSMIT) and len(results) == 8
 
@@ -150,7 +141,7 @@ def test_partial_slots_across_calls(sw, P, W):
     rng = np.random.default_rng(100 * W + P)
     mop = 2
     pair = Pair(sw, W, mop, P)
-    frames = window_frames(rng, pair, mop, range(mop))
+    frames = M.window_frames(rng, pair.P, pair.workers, mop, range(mop))
     for cut in range(len(frames) + 1):
         pair.reset()
         total = 0
@@ -176,12 +167,12 @@ def test_duplicates(sw):
     verdicts, results = pair.check([fr(0, 0), fr(0, 0), fr(1, 0), fr(1, 0, port=777), fr(2, 0), fr(0, 0, port=555),
                                     fr(1, 0, port=666)])
     assert verdicts.tolist() == [0, 0, 0, 0, 1, 2, 2]
-    assert bytes(results[5][0:6]) == A[0] and (int(results[5][36]) << 8 | int(results[5][37])) == 555
-    assert bytes(results[6][0:6]) == B[0] and (int(results[6][36]) << 8 | int(results[6][37])) == 666
-    assert np.array_equal(results[5][50:], results[4][50:])
+    assert FW.get(results[5], FW.DST_MAC) == A[0] and FW.get(results[5], FW.DST_PORT) == 555
+    assert FW.get(results[6], FW.DST_MAC) == B[0] and FW.get(results[6], FW.DST_PORT) == 666
+    assert np.array_equal(results[5][FW.EXP.start:], results[4][FW.EXP.start:])
     # in a later call
     verdicts, results = pair.check([fr(2, 0, port=444)])
-    assert verdicts.tolist() == [2] and bytes(results[0][0:6]) == C[0]
+    assert verdicts.tolist() == [2] and FW.get(results[0], FW.DST_MAC) == C[0]
     # the other workers move to the slot's other set: C's late question is still answered
     verdicts, _ = pair.check([fr(0, mop), fr(1, mop)])
     assert verdicts.tolist() == [0, 0]
@@ -200,7 +191,7 @@ def test_single_worker_answers_every_duplicate(sw):
          for p in range(4)]
     verdicts, results = pair.check([f[0], f[0], f[1], f[0]])
     assert verdicts.tolist() == [1, 2, 1, 2]
-    assert np.array_equal(results[3][50:], f[0][50:])
+    assert np.array_equal(results[3][FW.EXP.start:], f[0][FW.EXP.start:])
     verdicts, _ = pair.check([f[1], f[2], f[2], f[3]])
     assert verdicts.tolist() == [2, 1, 2, 4]                    # f[3]: slot 1's other set, after f[1] in this call
     verdicts, _ = pair.check([f[3], f[3]])
@@ -247,12 +238,12 @@ def test_ignored_frames(sw):
               M.worker_frame(P, pair.workers[1], 0, 0, pay)]
     verdicts, results = pair.check(frames)
     assert verdicts.tolist() == [0, 3, 3, 3, 1, 2]
-    assert pair.model.bitmap[0] == [3, 0] and bytes(results[4][48:50]) == b"\0\0"
+    assert pair.model.bitmap[0] == [3, 0] and FW.get(results[4], FW.POOL_INDEX) == 0
 
 
 def test_arithmetic(sw):
     """Sums that cross +-2^31 wrap; exponents are signed (negative, -128), and
-    byte 51 is maxed on its own."""
+    the second exponent is maxed on its own."""
     P, mop = 64, 4
     pair = Pair(sw, 3, mop, P)
     words = np.zeros((3, P), dtype=np.uint32)
@@ -271,10 +262,9 @@ def test_arithmetic(sw):
     assert int(np.sum(verdicts == M.BROADCAST)) == len(cases)
     for p, es in enumerate(cases):
         r = results[3 * p + 2]
-        got = r[52:].copy().view(">u4").astype(np.uint32)
-        assert np.array_equal(got, words[0] + words[1] + words[2])
-        assert r[50:52].copy().view(np.int8).tolist() == [max(e[0] for e in es), max(e[1] for e in es)]
-    assert results[2][52:56].copy().view(">u4")[0] == 0x80000000
+        assert np.array_equal(FW.payload_words(r, P), words[0] + words[1] + words[2])
+        assert r[FW.EXPS].copy().view(np.int8).tolist() == [max(e[0] for e in es), max(e[1] for e in es)]
+    assert FW.payload_words(results[2], P)[0] == 0x80000000
 
 
 @pytest.mark.parametrize("P,stride,out_stride,pinned", [
@@ -286,7 +276,7 @@ def test_layout(sw, P, stride, out_stride, pinned):
     rng = np.random.default_rng(P)
     mop = 3
     pair = Pair(sw, 4, mop, P)
-    frames = window_frames(rng, pair, mop, range(mop))
+    frames = M.window_frames(rng, pair.P, pair.workers, mop, range(mop))
     frames.insert(5, frames[0])
     verdicts, _ = pair.check(frames[:7], stride=stride, out_stride=out_stride, pinned=pinned)
     verdicts, _ = pair.check(frames[7:] + [frames[2]], stride=stride, out_stride=out_stride, pinned=pinned)
@@ -298,7 +288,7 @@ def test_unsupported_writes_nothing(sw):
     import torch
     P = 64
     pair = Pair(sw, 2, 4, P)
-    frames = window_frames(np.random.default_rng(8), pair, 4, range(2))
+    frames = M.window_frames(np.random.default_rng(8), pair.P, pair.workers, 4, range(2))
     fb = M.frame_bytes(P)
     d_in = torch.from_numpy(np.concatenate(frames)).cuda()
     d_out = torch.full((len(frames) * fb,), SENTINEL, dtype=torch.uint8, device="cuda")
@@ -337,10 +327,10 @@ def test_lossy_streams(sw, seed):
         deferred = [frames[i] for i in range(len(frames)) if verdicts[i] == M.DEFERRED]
         ndeferred += len(deferred)
         for i, r in results.items():
-            p = int(r[44:48].copy().view("<u4")[0])
+            p = FW.get(r, FW.PKT_ID)
             sent = [M.worker_frame(P, pair.workers[w], p, M.pool_index(p, mop), payloads[w, p], exps[w, p])
                     for w in range(W)]
-            assert np.array_equal(r[50:], aggregate(sent)), (p, int(verdicts[i]))
+            assert np.array_equal(r[FW.EXP.start:], aggregate(sent)), (p, int(verdicts[i]))
             if verdicts[i] == M.BROADCAST:
                 assert p not in answered
                 answered.add(p)
@@ -373,14 +363,14 @@ def switch_windows(pair, frame_sets, nframes, mop):
         assert idx.numel() == hi - lo and int((verdict == M.CONSUMED).sum()) == n - (hi - lo)
         got.append(out.view(-1, fb)[idx])
     res = torch.cat(got)
-    order = torch.argsort(res[:, 44:48].contiguous().view(torch.int32).flatten())
+    order = torch.argsort(res[:, FW.PKT_ID].contiguous().view(torch.int32).flatten())
     return res[order].contiguous().reshape(-1), res.shape[0]
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
 def test_end_to_end_float(sw, dtype):
     """W = 3 workers' slices: frames with own exponents -> switch -> the global
-    exponents from byte 50 of the results; frames quantized with those ->
+    exponents from the results' exponent byte; frames quantized with those ->
     switch (after reset) -> every worker's receive loop.  The output is the
     dequantized plane-level oracle switch, bit for bit, on all three workers."""
     import torch
@@ -397,7 +387,7 @@ def test_end_to_end_float(sw, dtype):
     res, nres = switch_windows(pair, own, B + mop, mop)
     assert nres == B + mop
     fb = M.frame_bytes(P)
-    gexp = res.view(-1, fb)[:B, 50].contiguous().view(torch.int8)
+    gexp = res.view(-1, fb)[:B, FW.EXP.start].contiguous().view(torch.int8)
     want_exps = O.switch_exps([O.exponents(x, P) for x in xs])
     assert len({tuple(O.exponents(x, P).tolist()) for x in xs}) == W  # the workers' exponents differ
     assert np.array_equal(gexp.cpu().numpy(), want_exps)

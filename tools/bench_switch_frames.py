@@ -34,8 +34,31 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "p4app-switchml_amd")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import switchml_amd as sw  # noqa: E402
+from switchml_amd import frame_wire as FW  # noqa: E402
 
 WORKERS = [(bytes([2, 0, 0, 0, 1, w]), f"10.0.1.{w + 1}") for w in range(8)]
+
+
+def header_block(S, W, P, set_bit, seed):
+    """The headers of frame_set's frames, up to the exponents, on the host:
+    one per (slot, worker) in a seeded arrival order, the fields a switch
+    reads.  Returns (hdr [S W, bytes before the exponents], slot, w)."""
+    F = S * W
+    order = np.random.default_rng(seed).permutation(F)
+    slot, w = order // W, order % W
+    hdr = np.zeros((F, FW.EXP.start), dtype=np.uint8)
+    FW.put(hdr, FW.ETHERTYPE, b"\x08\x00")
+    FW.put(hdr, FW.IP_VER_TOS, b"\x45\x00")
+    FW.put(hdr, FW.IP_PROTO, 17)
+    FW.put(hdr, FW.SRC_IP, FW.ip_bytes("10.0.1.0"))
+    hdr[:, FW.SRC_IP.stop - 1] = w + 1                               # 10.0.1.w+1, as WORKERS
+    FW.put(hdr, FW.DST_IP, FW.ip_bytes(FW.SWITCH_IP))
+    FW.put(hdr, FW.SRC_PORT, 4000 + w)
+    FW.put(hdr, FW.DST_PORT, 48879)
+    FW.put(hdr, FW.JOB_TYPE_SIZE, FW.job_type_size(P))
+    FW.put(hdr, FW.PKT_ID, slot)
+    FW.put(hdr, FW.POOL_INDEX, slot | (set_bit << 15))
+    return hdr, slot, w
 
 
 def frame_set(S, W, P, set_bit, seed, dev):
@@ -46,20 +69,8 @@ def frame_set(S, W, P, set_bit, seed, dev):
     g = torch.Generator(device=dev)
     g.manual_seed(seed)
     frames = torch.randint(0, 256, (F, fb), dtype=torch.uint8, device=dev, generator=g)
-    order = np.random.default_rng(seed).permutation(F)
-    slot, w = order // W, order % W
-    hdr = np.zeros((F, 52), dtype=np.uint8)
-    hdr[:, 12], hdr[:, 14], hdr[:, 23] = 0x08, 0x45, 17
-    hdr[:, 26:30] = np.array([10, 0, 1, 0], dtype=np.uint8)
-    hdr[:, 29] = w + 1
-    hdr[:, 30:34] = np.array([10, 0, 0, 253], dtype=np.uint8)
-    hdr[:, 34], hdr[:, 35] = (4000 + w) >> 8, (4000 + w) & 0xff
-    hdr[:, 36], hdr[:, 37] = 48879 >> 8, 48879 & 0xff
-    hdr[:, 42] = 0x13
-    hdr[:, 44:48] = slot.astype("<u4").view(np.uint8).reshape(F, 4)
-    idx = slot | (set_bit << 15)
-    hdr[:, 48], hdr[:, 49] = idx >> 8, idx & 0xff
-    frames[:, :50] = torch.from_numpy(hdr[:, :50]).to(dev)
+    hdr, slot, w = header_block(S, W, P, set_bit, seed)
+    frames[:, :FW.EXP.start] = torch.from_numpy(hdr).to(dev)
     return frames.reshape(-1), slot, w
 
 
@@ -74,9 +85,9 @@ def check_call(fs, frames, slot, S, W, P):
     assert counts.tolist() == [S * (W - 1), S, 0, 0, 0], counts.tolist()
     fr = frames.view(-1, fb)
     mine = np.flatnonzero(slot == 0)
-    words = fr[torch.from_numpy(mine).to(fr.device), 52:].cpu().numpy().view(">u4").astype(np.uint32).sum(axis=0, dtype=np.uint32)
+    words = FW.payload_words(fr[torch.from_numpy(mine).to(fr.device)].cpu().numpy(), P).sum(axis=0, dtype=np.uint32)
     i = int(mine[verdict[torch.from_numpy(mine).to(verdict.device)].cpu().numpy() == sw.VERDICT_BROADCAST][0])
-    got = out.view(-1, fb)[i, 52:].cpu().numpy().view(">u4").astype(np.uint32)
+    got = FW.payload_words(out.view(-1, fb)[i].cpu().numpy(), P)
     assert np.array_equal(got, words), "result words != sum of the slot's payloads"
 
 
@@ -204,7 +215,8 @@ def main_deliver(out_path=None, rounds=7, W=8, P=256, trace_only=False):
         src_frames = out.view(F, fb)[vd == sw.VERDICT_BROADCAST]
         for u in (0, W - 1):
             got = rings[u, :S]
-            assert torch.equal(got[:, 34:], src_frames[:, 34:]) and bool((got[:, 33] == u + 1).all())
+            assert torch.equal(got[:, FW.SRC_PORT.start:], src_frames[:, FW.SRC_PORT.start:])
+            assert bool((got[:, FW.DST_IP.stop - 1] == u + 1).all())             # 10.0.1.u+1
         fs.reset()
 
         def deliver_only(k, fs=fs, out=out, vd=vd, F=F, rings=rings):

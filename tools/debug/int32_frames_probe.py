@@ -8,6 +8,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import switchml_amd as sw  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+from switchml_amd import frame_wire as FW  # noqa: E402
+
+SHOWN = slice(FW.PKT_ID.start, FW.HEADER_BYTES + 32)       # the pkt_id, pool index, exponents, 8 payload words
 
 for n, P in ((1, 64), (300, 256), (8, 64)):
     x = np.arange(1, n + 1, dtype=np.int32) * 0x01020304
@@ -15,7 +18,7 @@ for n, P in ((1, 64), (300, 256), (8, 64)):
     ref = O.build_frames_i32(x, fp, P=P)
     got = sw.pack_frames_int32(torch.from_numpy(x).cuda(), fp, P).cpu().numpy()
     torch.cuda.synchronize()
-    print(n, P, "got", got[44:84].tolist())
-    print(n, P, "ref", ref[44:84].tolist())
+    print(n, P, "got", got[SHOWN].tolist())
+    print(n, P, "ref", ref[SHOWN].tolist())
     bad = np.nonzero(got != ref)[0]
     print("bad bytes", bad[:40].tolist(), "count", bad.size)

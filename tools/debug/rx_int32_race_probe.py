@@ -16,6 +16,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import switchml_amd as sw  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+from switchml_amd import frame_wire as FW  # noqa: E402
 from test_frames_int32 import altered_copies_stream, int32_data, python_rx  # noqa: E402
 
 
@@ -24,7 +25,7 @@ def main():
     P, n = 256, 8 * 1024 * 1024
     fp = sw.frame_params(job_id=5)
     x = int32_data(1, n)
-    fb = 52 + 4 * P
+    fb = FW.frame_bytes(P)
     B = O.num_blocks(n, P)
     out = []
     for gap in (16, 256, 4096):
