@@ -581,8 +581,10 @@ sml_status_t sml_pack_frames_int32(const int32_t* d_in, uint64_t numel, uint32_t
  * ntohl of the accepted frame's words into d_out[pkt_id*P ..
  * pkt_id*P + min(P, numel - pkt_id*P)).  d_state: uint64[2B + 6] (the rx
  * bitmap, the slice's call sequence, the slice's count of copies that
- * claimed ahead of an earlier copy, two alternating slots of a call's
- * conflict count and dirty-list length, then up to B listed pkt_ids),
+ * claimed ahead of an earlier copy, the conflict count and dirty-list length
+ * of the call in progress (0 between calls), the fix-up workgroups finished
+ * so far (128 per call), the list length the last call's fix-up found, then
+ * up to B listed pkt_ids),
  * zeroed per slice (sml_rx_reset), persists across calls; d_counts as for
  * sml_dequantize_frames.  One pass in stream order over the frames (an INT32
  * frame needs no other frame) plus a fix-up over a grid of workgroups that

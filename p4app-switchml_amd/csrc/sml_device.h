@@ -528,6 +528,48 @@ __device__ __forceinline__ void build_lut(float* lut, uint32_t W) {
     __syncthreads();
 }
 
+// ------------------------------------------------- per-workgroup tallies
+// A workgroup's small counts on their way to global 64-bit counters, through
+// a __shared__ uint32_t array the kernel declares: zeroed (tally_init, which
+// ends in the barrier), added to with LDS atomics (tally_add), and after a
+// second barrier flushed with one global atomic per non-zero bin
+// (tally_flush: thread i sends bin i to counts[first + i * step]).
+// Same-address global atomics from every thread serialize in one L2 channel;
+// this way a workgroup sends at most one per counter, and none for a zero.
+template <int N>
+__device__ __forceinline__ void tally_init(uint32_t (&bins)[N]) {
+    if (threadIdx.x < N) bins[threadIdx.x] = 0;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void tally_add(uint32_t& bin, uint32_t v) {
+    if (v) atomicAdd(&bin, v);
+}
+
+template <int N>
+__device__ __forceinline__ void tally_flush(const uint32_t (&bins)[N], unsigned long long* counts, uint32_t first = 0,
+                                            uint32_t step = 1) {
+    __syncthreads();
+    if (threadIdx.x < N && bins[threadIdx.x])
+        atomicAdd(counts + first + threadIdx.x * step, (unsigned long long)bins[threadIdx.x]);
+}
+
+// The receive kernels' ending, counts = {accepted, discarded} with the
+// workgroup's discards tallied in bins[0]: accepted = frames - discarded, so
+// workgroup 0 adds the frame count once and only workgroups that saw a
+// discard touch the counters.
+__device__ __forceinline__ void tally_flush_accepted(const uint32_t (&bins)[1], unsigned long long* counts,
+                                                     uint64_t nframes) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t disc = bins[0];
+        unsigned long long acc = blockIdx.x == 0 ? (unsigned long long)nframes : 0ull;
+        acc -= disc;                                                 // mod 2^64
+        if (acc) atomicAdd(counts + 0, acc);
+        if (disc) atomicAdd(counts + 1, (unsigned long long)disc);
+    }
+}
+
 // ------------------------------------------------------- launch geometry
 
 // The wave's index in its workgroup, as a wave-uniform (SGPR) value, so that

@@ -13,9 +13,9 @@ namespace sml {
 
 // Pass 1, thread per frame: frames of another job, out-of-range or already
 // received pkt_ids are discarded; the others claim their pkt_id.  Counting:
-// accepted = frames - discarded, so block 0 adds the frame count once and only
-// workgroups that saw a discard touch the counters (same-address atomics from
-// every workgroup serialize in one L2 channel: ~40 us at 262 k frames).
+// the workgroup's discards, tallied and sent by tally_flush_accepted
+// (sml_device.h; same-address atomics from every workgroup serialize in one
+// L2 channel: ~40 us at 262 k frames).
 __global__ __launch_bounds__(kBlockThreads) void k_rx_claim(RxArgs a) {
     const uint64_t stride = (uint64_t)gridDim.x * kBlockThreads;
     const uint64_t f0 = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x;
@@ -27,9 +27,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_claim(RxArgs a) {
         }
         return;
     }
-    __shared__ uint32_t disc;
-    if (threadIdx.x == 0) disc = 0;
-    __syncthreads();
+    __shared__ uint32_t disc[1];
+    tally_init(disc);
     uint32_t mine = 0;
     for (uint64_t f = f0; f < a.nframes; f += stride) {
         const RxHdr h = rx_header(a, f);
@@ -37,14 +36,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_claim(RxArgs a) {
         const unsigned long long v = ((unsigned long long)rx_tag(f) << 32) | h.exp;
         if (atomicMax(a.state + h.pid, v) != 0ull) mine++;          // duplicate or received earlier
     }
-    if (mine) atomicAdd(&disc, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long acc = blockIdx.x == 0 ? (unsigned long long)a.nframes : 0ull;
-        acc -= disc;                                                 // mod 2^64
-        if (acc) atomicAdd(a.counts + 0, acc);
-        if (disc) atomicAdd(a.counts + 1, (unsigned long long)disc);
-    }
+    tally_add(disc[0], mine);
+    tally_flush_accepted(disc, a.counts, a.nframes);
 }
 
 // --------------------------------------- INT32 job slices, receive side
@@ -54,15 +47,22 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_claim(RxArgs a) {
 // ppp.cc:65-67; PostprocessSingle's INT32 branch, ppp.cc:262-298) — so one
 // pass in stream order decides and writes each frame: no claim pass over the
 // headers, no second walk in block order.  State: uint64[2B + 6] per slice:
-// [0, B) the rx bitmap, [B] the call sequence c of this slice, [B + 1] the
-// conflicts resolved in the slice so far (a statistic: copies that arrived
-// ahead of an earlier one), [B + 2 + (c & 1)] the conflict count of call c,
-// [B + 4 + (c & 1)] the length of call c's dirty list, [B + 6, 2B + 6) that
-// list: the pkt_ids marked dirty in call c (appended by the claim that sets
-// a pkt_id's dirty bit), so the fix-up visits only them.  The per-call
-// counters alternate between two slots so that the fix-up's workgroups can
-// all read call c's without a grid-wide barrier: the fix-up of call c clears
-// the OTHER slot (call c - 1's, whose fix-up has ended), ready for c + 1.
+// [0, B) the claim words (the rx bitmap), then six header words, kRx* below:
+//   [B]      the call sequence c of this slice;
+//   [B + 1]  the conflicts resolved in the slice so far (a statistic: copies
+//            that arrived ahead of an earlier one);
+//   [B + 2]  the conflicts of the call in progress, 0 between calls;
+//   [B + 3]  the length of that call's dirty list (past B: it overflowed),
+//            0 between calls;
+//   [B + 4]  arrivals: the fix-up workgroups that have finished over the
+//            slice's life, never reset: kRxFixupBlocks * c between calls;
+//   [B + 5]  what [B + 3] held when the last finished call's fix-up ended (a
+//            statistic: whether that fix-up walked the list or scanned);
+// and [B + 6, 2B + 6) the dirty list: the pkt_ids marked dirty in the call
+// (appended by the claim that sets a pkt_id's dirty bit), so the fix-up
+// visits only them.  The fix-up's workgroups all read the call's counters at
+// their start; the one that finishes last clears them and advances c
+// (k_rx_int32_fixup).
 // A frame's tag is
 //   (0xFFFFFFFF - c) << 32 | (0x7FFFFFFF - f) << 1      (bit 0: dirty),
 // larger for an earlier call and, within a call, for an earlier frame f, so
@@ -89,6 +89,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_claim(RxArgs a) {
 // for any payloads.
 constexpr uint32_t kRxI32MaxFrames = 0x7FFFFFFFu;
 constexpr uint32_t kRxFixupBlocks = 128;   // k_rx_int32_fixup's grid
+// The header words of an INT32 slice's state, as offsets from state + B.
+constexpr uint32_t kRxCall = 0, kRxTotal = 1, kRxConflicts = 2, kRxListed = 3, kRxArrivals = 4, kRxLastListed = 5,
+                   kRxList = 6;
 
 __host__ __device__ constexpr int rx_int32_slices(int P) { return P / 256 > 4 ? P / 256 : 4; }
 
@@ -141,9 +144,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_int32(RxArgs a) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
     const uint64_t ntiles = (a.nframes + kF - 1) / kF;
-    const uint32_t call = (uint32_t)a.state[a.nblocks];
-    unsigned long long* const conflicts = a.state + a.nblocks + 2 + (call & 1u);
-    unsigned long long* const listed = a.state + a.nblocks + 4 + (call & 1u);
+    unsigned long long* const hdr = a.state + a.nblocks;
+    const uint32_t call = (uint32_t)hdr[kRxCall];
     uint32_t disc = 0;
     uint64_t t = xcd_block(a.xcd) * kWavesPerBlock + wave_index();
     RxI32Tile<P> cur, nxt;
@@ -167,10 +169,10 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_int32(RxArgs a) {
                     keep = true;
                 } else if ((old & ~1ull) < tag) {
                     write = true;
-                    atomicAdd(conflicts, 1ull);
+                    atomicAdd(hdr + kRxConflicts, 1ull);
                     if (!(atomicOr(a.state + pid, 1ull) & 1ull)) {   // this claim made it dirty: list it
-                        const unsigned long long i = atomicAdd(listed, 1ull);
-                        if (i < a.nblocks) a.state[a.nblocks + 6 + i] = pid;
+                        const unsigned long long i = atomicAdd(hdr + kRxListed, 1ull);
+                        if (i < a.nblocks) hdr[kRxList + i] = pid;
                     }
                 }
             }
@@ -200,19 +202,10 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_int32(RxArgs a) {
         cur = nxt;
     }
     if (!a.counts) return;
-    // accepted = frames - discarded: block 0 adds the frame count once, and
-    // only workgroups that saw a discard touch the discard counter
-    __shared__ uint32_t bdisc;
-    if (threadIdx.x == 0) bdisc = 0;
-    __syncthreads();
-    if (disc) atomicAdd(&bdisc, disc);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long acc = blockIdx.x == 0 ? (unsigned long long)a.nframes : 0ull;
-        acc -= bdisc;                                                // mod 2^64
-        if (acc) atomicAdd(a.counts + 0, acc);
-        if (bdisc) atomicAdd(a.counts + 1, (unsigned long long)bdisc);
-    }
+    __shared__ uint32_t bdisc[1];
+    tally_init(bdisc);
+    tally_add(bdisc[0], disc);
+    tally_flush_accepted(bdisc, a.counts, a.nframes);
 }
 
 // Rewrite dirty pkt_id k from the frame its tag names (the first copy), the
@@ -226,17 +219,30 @@ __device__ __forceinline__ void rx_int32_rewrite(const RxArgs& a, uint32_t P, ui
     for (uint64_t i = lane; i < valid; i += kWave) dst[i] = bswap(src[i]);
 }
 
-// kRxFixupBlocks workgroups, after k_rx_int32 on the same stream: with
-// conflicts in this call, every dirty pkt_id is rewritten from the frame its
-// tag names (the first copy) and cleaned; the slice's conflict total
-// accumulates, the other counter slot is cleared and the call sequence
-// advanced.  Without conflicts (no copies claimed out of order) it only does
-// the last three.
+// kRxFixupBlocks workgroups, after k_rx_int32 on the same stream.  Every
+// workgroup reads the call's sequence c, conflict count n and list length at
+// its start; with conflicts (n != 0) it takes its share of the dirty pkt_ids,
+// each rewritten from the frame its tag names (the first copy) and cleaned.
+// Then it draws a ticket from the arrivals word, and the workgroup that draws
+// the launch's last one runs the epilogue: the slice's total accumulates, the
+// list length is kept as a statistic, the call's two counters are cleared and
+// c advances.  Without conflicts that is all a launch does.
+//
+// The ticket is one relaxed agent-scope atomic per workgroup, with no release
+// or acquire fence, because it hands no data over: the last arriver reads
+// nothing that another workgroup of this launch wrote.  What it orders is
+// only that the epilogue's stores come after every workgroup's reads of c, n
+// and the list length, and they do: those reads precede the workgroup's own
+// ticket in program order (the work branches on them, and the barrier before
+// the ticket has every wave past that work), and the epilogue follows the
+// last ticket.  The next call sees the epilogue's stores by stream order.
+// The arrivals word only ever grows, kRxFixupBlocks per launch, so nothing
+// has to reset it between calls.
 __global__ __launch_bounds__(kBlockThreads) void k_rx_int32_fixup(RxArgs a, uint32_t P) {
-    const unsigned long long call = a.state[a.nblocks];
-    const uint32_t slot = (uint32_t)call & 1u;
-    const unsigned long long n = a.state[a.nblocks + 2 + slot];
-    const unsigned long long listed = a.state[a.nblocks + 4 + slot];
+    unsigned long long* const hdr = a.state + a.nblocks;
+    const unsigned long long call = hdr[kRxCall];
+    const unsigned long long n = hdr[kRxConflicts];
+    const unsigned long long listed = hdr[kRxListed];
     const int lane = threadIdx.x & (kWave - 1);
     const uint64_t wave = (uint64_t)blockIdx.x * kWavesPerBlock + wave_index();
     const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
@@ -245,7 +251,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_int32_fixup(RxArgs a, uint
         // the bit set rewrites the block, then cleans the bit (an id listed
         // twice is rewritten twice with the same words, or found clean)
         for (uint64_t i = wave; i < listed; i += nwaves) {
-            const uint64_t k = a.state[a.nblocks + 6 + i];
+            const uint64_t k = hdr[kRxList + i];
             const unsigned long long s = a.state[k];
             if (s & 1ull) {
                 rx_int32_rewrite(a, P, k, s, lane);
@@ -268,16 +274,16 @@ __global__ __launch_bounds__(kBlockThreads) void k_rx_int32_fixup(RxArgs a, uint
             if (s & 1ull) a.state[k] = s & ~1ull;
         }
     }
-    // one thread of the grid: the slice's total, the other slot cleared (call
-    // c - 1's: its fix-up has ended) for call c + 1, the sequence advanced.
-    // No workgroup of this launch reads those words after its start, and the
-    // next rx call runs after the whole launch (stream order).
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (n) a.state[a.nblocks + 1] += n;
-        a.state[a.nblocks + 2 + (slot ^ 1u)] = 0ull;
-        a.state[a.nblocks + 4 + (slot ^ 1u)] = 0ull;
-        a.state[a.nblocks] = call + 1;
-    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const unsigned long long ticket =
+        __hip_atomic_fetch_add(hdr + kRxArrivals, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket % kRxFixupBlocks != kRxFixupBlocks - 1) return;
+    if (n) hdr[kRxTotal] += n;
+    hdr[kRxLastListed] = listed;
+    hdr[kRxConflicts] = 0ull;
+    hdr[kRxListed] = 0ull;
+    hdr[kRxCall] = call + 1;
 }
 
 }  // namespace sml
@@ -291,7 +297,7 @@ uint64_t sml_frame_bytes(uint32_t packet_numel) { return wire::frame_bytes(packe
 uint64_t sml_rx_state_words(uint64_t numel, uint32_t packet_numel, uint32_t batch_max, int int32) {
     if (!valid_packet(packet_numel)) return 0;
     const uint64_t B = sml_num_blocks(numel, packet_numel);
-    if (int32) return 2 * B + 6;   // bitmap, sequence, conflict counts, dirty list (k_rx_int32)
+    if (int32) return 2 * B + kRxList;   // claim words, header words, dirty list (k_rx_int32)
     const uint64_t w = B + (B < batch_max ? B : batch_max);
     return w ? w : 1;
 }
@@ -405,7 +411,7 @@ static sml_status_t dequantize_frames(const void* frames, uint64_t num_frames, u
     if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
     const uint64_t elem = dt == SML_FLOAT32 ? 4 : 2;
     if ((uintptr_t)d_out & (elem - 1)) return SML_ERR_ALIGNMENT;
-    if (((uintptr_t)d_state & 7u) || (d_counts && ((uintptr_t)d_counts & 7u))) return SML_ERR_ALIGNMENT;
+    if (!aligned8(d_state) || !aligned8(d_counts)) return SML_ERR_ALIGNMENT;
     RxArgs a = rx_args(frames, num_frames, stride, numel, P, job_id, d_state, d_counts);
     const uint32_t U = (uint32_t)rx_slices((int)P);
     a.xcd = xcd_chunk_for(U);
@@ -501,7 +507,7 @@ sml_status_t sml_unpack_frames_int32(const void* frames, uint64_t num_frames, ui
     if (!d_state || (numel && !d_out)) return SML_ERR_INVALID_ARG;
     if (const sml_status_t s = check_frames(frames, stride, P); s != SML_OK) return s;
     if (!aligned4(d_out)) return SML_ERR_ALIGNMENT;
-    if (((uintptr_t)d_state & 7u) || (d_counts && ((uintptr_t)d_counts & 7u))) return SML_ERR_ALIGNMENT;
+    if (!aligned8(d_state) || !aligned8(d_counts)) return SML_ERR_ALIGNMENT;
     RxArgs a = rx_args(frames, num_frames, stride, numel, P, job_id, d_state, d_counts);
     a.xcd = g_xcd_chunk.load(std::memory_order_relaxed);
     a.b = 0;                                                  // INT32: no extra batch
@@ -523,7 +529,7 @@ sml_status_t sml_unpack_frames_int32(const void* frames, uint64_t num_frames, ui
 
 sml_status_t sml_rx_reset(uint64_t* d_state, uint64_t num_words, void* stream) {
     if (num_words == 0) return SML_OK;
-    if (!d_state || ((uintptr_t)d_state & 7u)) return SML_ERR_INVALID_ARG;
+    if (!d_state || !aligned8(d_state)) return SML_ERR_INVALID_ARG;
     return hip_check(hipMemsetAsync(d_state, 0, num_words * 8, (hipStream_t)stream));
 }
 

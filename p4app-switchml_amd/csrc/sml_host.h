@@ -39,6 +39,7 @@ inline bool valid_packet(uint32_t P) {
 inline bool is_half(sml_data_type_t dt) { return dt == SML_FLOAT16 || dt == SML_BFLOAT16; }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0; }
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 // The XCD chunk for tiles of U slices: XCD runs keep their byte length

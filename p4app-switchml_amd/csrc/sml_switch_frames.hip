@@ -126,9 +126,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_fs_claim(FsArgs a) {
 // frame f sees is the call's starting count stepped once per new contributor
 // of its set claimed below f.
 __global__ __launch_bounds__(kBlockThreads) void k_fs_verdict(FsArgs a) {
-    __shared__ uint32_t hist[5];
-    if (threadIdx.x < 5) hist[threadIdx.x] = 0;
-    __syncthreads();
+    __shared__ uint32_t hist[5];                              // frames per verdict
+    tally_init(hist);
     const uint64_t stride = (uint64_t)gridDim.x * kBlockThreads;
     for (uint64_t f = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x; f < a.nframes; f += stride) {
         const FsHdr h = fs_header(a, f);
@@ -163,11 +162,10 @@ __global__ __launch_bounds__(kBlockThreads) void k_fs_verdict(FsArgs a) {
         }
         a.verdict[f] = (uint8_t)verdict;
         if (lists) a.touched[atomicAdd(a.touched_count, 1u)] = h.s;
-        if (a.counts) atomicAdd(&hist[verdict], 1u);
+        if (a.counts) tally_add(hist[verdict], 1u);
     }
     if (!a.counts) return;
-    __syncthreads();
-    if (threadIdx.x < 5 && hist[threadIdx.x]) atomicAdd(a.counts + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
+    tally_flush(hist, a.counts);
 }
 
 __device__ __forceinline__ int fs_max_i8(uint32_t a, uint32_t b) {
@@ -412,8 +410,7 @@ struct FdArgs {
 // one group.
 __global__ __launch_bounds__(kBlockThreads) void k_fd_count(FdArgs a) {
     __shared__ uint32_t lost[2];                               // dropped, unroutable
-    if (threadIdx.x < 2) lost[threadIdx.x] = 0;
-    __syncthreads();
+    tally_init(lost);
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t all = 0xffffffffu >> (32 - a.W);
     const uint64_t nblocks = (a.nframes + kBlockThreads - 1) / kBlockThreads;
@@ -444,14 +441,12 @@ __global__ __launch_bounds__(kBlockThreads) void k_fd_count(FdArgs a) {
         const uint64_t g = b * kWavesPerBlock + wave_index();
         if (lane < a.W && g < a.ngroups) a.prefix[lane * a.group_stride + g] = mine;
         if (a.counts) {
-            if (dropped) atomicAdd(&lost[0], dropped);
-            if (unroutable) atomicAdd(&lost[1], 1u);
+            tally_add(lost[0], dropped);
+            tally_add(lost[1], unroutable ? 1u : 0u);
         }
     }
     if (!a.counts) return;
-    __syncthreads();
-    if (threadIdx.x < 2 && lost[threadIdx.x])
-        atomicAdd(a.counts + (threadIdx.x == 0 ? 1 : 3), (unsigned long long)lost[threadIdx.x]);
+    tally_flush(lost, a.counts, 1, 2);                         // counts[1], counts[3]
 }
 
 // Pass 2, workgroup u: worker u's group counts -> their exclusive prefix, in
@@ -603,7 +598,7 @@ sml_status_t sml_frame_switch_reset(void* d_state, uint32_t num_slots, uint32_t 
     if (!d_state) return SML_ERR_INVALID_ARG;
     FsLayout l;
     if (!fs_layout(num_slots, packet_numel, l)) return SML_ERR_UNSUPPORTED;
-    if ((uintptr_t)d_state & 7u) return SML_ERR_ALIGNMENT;
+    if (!aligned8(d_state)) return SML_ERR_ALIGNMENT;
     // everything but the accumulators: a slot's words are written before they are read
     return hip_check(hipMemsetAsync(d_state, 0, l.acc, (hipStream_t)stream));
 }
@@ -619,7 +614,7 @@ sml_status_t sml_frame_switch(const sml_frame_switch_params* prm, const void* fr
     if (num_frames == 0) return SML_OK;
     if (!wire::frame_set_fits(frames, stride, P)) return SML_ERR_ALIGNMENT;
     if (!wire::frame_set_fits(out_frames, out_stride, P)) return SML_ERR_ALIGNMENT;
-    if (((uintptr_t)d_state & 7u) || (d_counts && ((uintptr_t)d_counts & 7u))) return SML_ERR_ALIGNMENT;
+    if (!aligned8(d_state) || !aligned8(d_counts)) return SML_ERR_ALIGNMENT;
 
     FsArgs a;
     memset(&a, 0, sizeof(a));
@@ -681,8 +676,7 @@ sml_status_t sml_frame_switch_deliver(const sml_frame_switch_params* prm, const 
     if (!wire::frame_set_fits(out_frames, out_stride, P)) return SML_ERR_ALIGNMENT;
     if (!wire::frame_set_fits(rings, rx_stride, P) || ring_bytes % 4) return SML_ERR_ALIGNMENT;
     if (ring_frames > ~0ull / rx_stride || ring_bytes < ring_frames * rx_stride) return SML_ERR_ALIGNMENT;
-    if (!aligned4(d_drop) || ((uintptr_t)d_ring_count & 7u) || ((uintptr_t)d_counts & 7u) ||
-        ((uintptr_t)d_scratch & 15u))
+    if (!aligned4(d_drop) || !aligned8(d_ring_count) || !aligned8(d_counts) || !aligned16(d_scratch))
         return SML_ERR_ALIGNMENT;
 
     const FdLayout l = fd_layout(num_frames, W);
@@ -728,7 +722,7 @@ sml_status_t sml_frame_gather(const void* const* sets, uint32_t num_sets, uint64
     for (uint32_t s = 0; s < num_sets; s++)
         if (!wire::frame_set_fits(sets[s], set_stride, packet_numel)) return SML_ERR_ALIGNMENT;
     if (!wire::frame_set_fits(dst, dst_stride, packet_numel)) return SML_ERR_ALIGNMENT;
-    if (!aligned4(d_set) || ((uintptr_t)d_index & 7u) || ((uintptr_t)d_skipped & 7u)) return SML_ERR_ALIGNMENT;
+    if (!aligned4(d_set) || !aligned8(d_index) || !aligned8(d_skipped)) return SML_ERR_ALIGNMENT;
 
     FgArgs a;
     memset(&a, 0, sizeof(a));

@@ -885,15 +885,25 @@ def pack_frames_int32(x, params: FrameParams, packet_numel: int = 256, frames=No
 
 class RxSliceInt32:
     """Receive-side state of one INT32 job slice for unpack_frames_int32: the
-    rx bitmap over its B pkt_ids plus the slice's call sequence, the running
-    call's conflict count, the slice's conflict total and the fix-up's dirty
+    rx bitmap over its B pkt_ids, six header words and the fix-up's dirty
     list (uint64[2B + 6], sml_rx_state_words), {accepted, discarded}
-    counters, the output."""
+    counters, the output.
+
+    The header words' indices into `state` (sml_frames.hip, kRx*): CALL the
+    slice's call sequence, TOTAL the conflicts resolved so far, CONFLICTS and
+    LISTED the conflict count and dirty-list length of the call in progress
+    (0 between calls), ARRIVALS the fix-up workgroups finished over the
+    slice's life (FIXUP_BLOCKS per call), LAST_LISTED what LISTED held when
+    the last call's fix-up ended; LIST is the dirty list's first word."""
+
+    FIXUP_BLOCKS = 128          # k_rx_int32_fixup's grid (kRxFixupBlocks)
 
     def __init__(self, numel: int, packet_numel: int = 256, device="cuda", out=None):
         torch = _torch()
         self.numel, self.packet_numel = numel, packet_numel
         self.nblocks = num_blocks(numel, packet_numel)
+        (self.CALL, self.TOTAL, self.CONFLICTS, self.LISTED, self.ARRIVALS, self.LAST_LISTED,
+         self.LIST) = range(self.nblocks, self.nblocks + 7)
         self.state = torch.zeros(int(lib().sml_rx_state_words(numel, packet_numel, 1, 1)), dtype=torch.int64,
                                  device=device)
         self.counts = torch.zeros(2, dtype=torch.int64, device=device)
@@ -903,7 +913,7 @@ class RxSliceInt32:
     def conflicts(self) -> int:
         """Copies of a pkt_id that claimed it ahead of an earlier copy and were
         resolved by the fix-up, over the slice so far (reads the device)."""
-        return int(self.state[self.nblocks + 1].item())
+        return int(self.state[self.TOTAL].item())
 
     def reset(self, stream=None):
         """rte_bitmap_reset for a new job slice (sml_rx_reset)."""

@@ -307,7 +307,9 @@ def test_int32_rx_first_copy_wins_over_racing_copies(cuda, P, n, pairs):
     assert bad.size == 0, (bad.size, bad[:8].tolist())
     assert rx.counts.cpu().tolist() == [acc, dis] and acc == B and dis == pairs
     st = rx.state.cpu().numpy()
-    assert st[B] == 1 and st[B + 3] == 0 and st[B + 5] == 0   # call sequence advanced, call 1's slot clear
+    assert st[rx.CALL] == 1                                    # call sequence advanced
+    assert st[rx.CONFLICTS] == 0 and st[rx.LISTED] == 0        # the call's counters cleared by its own fix-up
+    assert st[rx.ARRIVALS] == rx.FIXUP_BLOCKS                  # every fix-up workgroup drew its ticket
     assert not (st[:B] & 1).any()                              # no dirty pkt_id left
     print(f"P={P}: {rx.conflicts} of {pairs} copies claimed ahead of an earlier copy")
 
@@ -405,10 +407,11 @@ def test_int32_rx_fixup_rewrites_displaced_claims(cuda, P, overflow):
     race to the atomic) and their output words hold that copy's garbage.  The
     real (earlier) frames must displace those claims, mark them dirty, and
     the fix-up must leave the earlier frames' words, clean state words, the
-    conflict count in the slice total, and the call sequence advanced.  The
-    fix-up visits the call's dirty list (state[B + 4 ...], ADVICE r5);
-    overflow=True plants a full list first, so every append is dropped and
-    the fix-up takes its fallback, the scan of all B state words."""
+    conflict count in the slice total, the call's own counters cleared, one
+    ticket drawn per fix-up workgroup and the call sequence advanced.  The
+    fix-up visits the call's dirty list (state[rx.LIST ...], ADVICE r5);
+    overflow=True plants a full list first (rx.LISTED), so every append is
+    dropped and the fix-up takes its fallback, the scan of all B state words."""
     import torch
     import switchml_amd as sw
     n = 40_000 + 7
@@ -425,7 +428,7 @@ def test_int32_rx_fixup_rewrites_displaced_claims(cuda, P, overflow):
     for k in stolen:                                    # frame k's later twin (index B + k) claimed k first
         st[k] = claim_tag(0, B + int(k))
     if overflow:
-        st[B + 4] = B                                   # call 0's list is full: the fix-up must scan
+        st[rx.LISTED] = B                               # the call's list is full: the fix-up must scan
     rx.state.copy_(torch.from_numpy(st))
     rx.out.fill_(-1)
     sw.unpack_frames_int32(torch.from_numpy(frames).to(cuda), B, rx, job_id=4)
@@ -433,12 +436,13 @@ def test_int32_rx_fixup_rewrites_displaced_claims(cuda, P, overflow):
     assert np.array_equal(rx.out.cpu().numpy(), x)
     st = rx.state.cpu().numpy()
     assert not (st[:B] & 1).any()
-    # sequence, slice total, call 0's conflict count and list length (left:
-    # the next fix-up clears them), call 1's (cleared)
-    assert [int(v) for v in st[B:B + 6]] == [1, len(stolen), len(stolen), 0,
-                                             B + len(stolen) if overflow else len(stolen), 0]
+    # sequence, slice total (0 before: the call's conflict count is its
+    # increase), the call's counters (cleared by its own fix-up), a ticket per
+    # fix-up workgroup, the list length the fix-up found
+    assert [int(v) for v in st[rx.CALL:rx.LIST]] == [1, len(stolen), 0, 0, rx.FIXUP_BLOCKS,
+                                                     B + len(stolen) if overflow else len(stolen)]
     if not overflow:                                    # each displaced pkt_id listed once, in some order
-        assert sorted(int(v) for v in st[B + 6:B + 6 + len(stolen)]) == [int(k) for k in stolen]
+        assert sorted(int(v) for v in st[rx.LIST:rx.LIST + len(stolen)]) == [int(k) for k in stolen]
     assert rx.conflicts == len(stolen)
     # displaced claims count as the discards (their twins were counted accepted)
     assert rx.counts.cpu().tolist() == [B - len(stolen), len(stolen)]
@@ -448,7 +452,82 @@ def test_int32_rx_fixup_rewrites_displaced_claims(cuda, P, overflow):
     torch.cuda.synchronize()
     assert not rx.out.cpu().numpy().any()
     assert rx.counts.cpu().tolist() == [B - len(stolen), B + len(stolen)]
-    assert int(rx.state[B].item()) == 2
+    assert rx.state[rx.CALL:rx.LIST].cpu().tolist() == [2, len(stolen), 0, 0, 2 * rx.FIXUP_BLOCKS, 0]
+
+
+def conflict_calls(cuda, P, before_call=lambda: None):
+    """Four rx calls on one state without a reset, each with conflicts: the
+    slice's pkt_ids in 4 disjoint groups, call c receives group c's frames,
+    and a fifth of the group's pkt_ids hold the claim tag of a LATER frame of
+    call c beforehand (as in test_int32_rx_fixup_rewrites_displaced_claims).
+    After every call the whole header is checked — an odd call's bookkeeping
+    like an even one's — with the dirty bits, the list, the output and the
+    counts.  `before_call` runs right before each rx call is enqueued."""
+    import torch
+    import switchml_amd as sw
+    n = 40_000 + 7
+    fp = params(job_id=4)
+    x = int32_data(P + 3, n)
+    fb = FW.frame_bytes(P)
+    B = O.num_blocks(n, P)
+    fr = O.build_frames_i32(x, fp, P=P).reshape(B, fb)
+    rng = np.random.default_rng(P + 1)
+    groups = [np.sort(g) for g in np.array_split(rng.permutation(B), 4)]
+    rx = sw.RxSliceInt32(n, P, device=cuda)
+    rx.reset()
+    rx.out.fill_(-1)
+    want = np.full(n, -1, dtype=np.int32)
+    total = acc = dis = 0
+    for c, grp in enumerate(groups):
+        planted = np.sort(rng.choice(grp, max(1, len(grp) // 5), replace=False))
+        tags = [claim_tag(c, len(grp) + j) for j in range(len(planted))]      # frames past the call's last
+        rx.state[torch.from_numpy(planted).to(cuda)] = torch.tensor(tags, dtype=torch.int64, device=cuda)
+        before_call()
+        sw.unpack_frames_int32(torch.from_numpy(fr[grp].reshape(-1)).to(cuda), len(grp), rx, job_id=4)
+        torch.cuda.synchronize()
+        for k in grp.tolist():
+            want[k * P:(k + 1) * P] = x[k * P:(k + 1) * P]
+        total, acc, dis = total + len(planted), acc + len(grp) - len(planted), dis + len(planted)
+        st = rx.state.cpu().numpy()
+        assert [int(v) for v in st[rx.CALL:rx.LIST]] == [c + 1, total, 0, 0, (c + 1) * rx.FIXUP_BLOCKS,
+                                                         len(planted)], c
+        assert not (st[:B] & 1).any(), c
+        assert sorted(int(v) for v in st[rx.LIST:rx.LIST + len(planted)]) == planted.tolist(), c
+        assert np.array_equal(rx.out.cpu().numpy(), want), c
+        assert rx.counts.cpu().tolist() == [acc, dis], c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [64, 256, 1024])
+def test_int32_rx_conflict_calls_without_reset(cuda, P):
+    """Deterministic: conflict_calls on an otherwise idle device.  Pins the
+    per-call bookkeeping (counters cleared by the call's own fix-up, one
+    ticket per fix-up workgroup, the sequence) over odd and even calls."""
+    conflict_calls(cuda, P)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [64, 256, 1024])
+def test_int32_rx_conflict_calls_busy_device_smoke(cuda, P):
+    """A SMOKE TEST of real scheduling, not the pin of the bookkeeping (that
+    is test_int32_rx_conflict_calls_without_reset): the same four calls while
+    a second stream runs the fused round trip on a 64 Mi-element bucket,
+    launched a few times ahead of every rx call, so that the fix-up's
+    workgroups may be dispatched late and apart.  Asserted: everything
+    conflict_calls asserts, whatever the scheduling did.  NOT asserted: that
+    the two streams actually overlapped — the hardware decides."""
+    import torch
+    import switchml_amd as sw
+    side = torch.cuda.Stream(device=cuda)
+    big = torch.zeros(64 << 20, dtype=torch.float32, device=cuda)
+    out = torch.empty_like(big)
+    side.wait_stream(torch.cuda.current_stream(cuda))
+
+    def busy():
+        for _ in range(4):
+            sw.roundtrip_loopback(big, out=out, stream=side)
+
+    conflict_calls(cuda, P, before_call=busy)
 
 
 @pytest.mark.gpu
@@ -480,7 +559,7 @@ def test_int32_rx_many_calls_keep_earlier_winners(cuda):
     torch.cuda.synchronize()
     assert np.array_equal(rx.out.cpu().numpy(), ref)
     assert rx.counts.cpu().tolist() == [acc, dis]
-    assert int(rx.state[B].item()) == len(bounds) - 1
+    assert int(rx.state[rx.CALL].item()) == len(bounds) - 1
 
 
 @pytest.mark.gpu
@@ -575,7 +654,7 @@ def test_int32_rx_random_streams(cuda):
             torch.cuda.synchronize()
             assert np.array_equal(rx.out.cpu().numpy(), ref), (n, P, lo, hi)
             assert rx.counts.cpu().tolist() == [acc, dis], (n, P, lo, hi)
-        assert int(rx.state[O.num_blocks(n, P)].item()) == len(bounds) - 1          # call sequence
+        assert int(rx.state[rx.CALL].item()) == len(bounds) - 1                     # call sequence
     check()
 
 

@@ -50,7 +50,7 @@ def main(K=1000, reps=10):
             if mode != "clean":
                 rx.state[stolen] = tags
             if mode == "scan":
-                rx.state[B + 3] = B
+                rx.state[rx.LISTED] = B
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             a.record()
@@ -60,6 +60,8 @@ def main(K=1000, reps=10):
             ts.append(a.elapsed_time(b) * 1e3)
             assert torch.equal(rx.out, x), mode
             assert rx.conflicts == (0 if mode == "clean" else K), (mode, rx.conflicts)
+            # the mode ran: the list length the fix-up found (past B: it scanned)
+            assert int(rx.state[rx.LAST_LISTED].item()) == {"clean": 0, "list": K, "scan": B + K}[mode], mode
         out[mode] = {"call_us_median": round(float(np.median(ts)), 2), "call_us": [round(t, 2) for t in ts]}
     print(json.dumps(out))
 
