@@ -8,47 +8,12 @@ from __future__ import annotations
 
 import ctypes
 
-from . import lib as _kernel_lib
+from .abi import lib
 
 CREATED, STARTING, RUNNING, STOPPING, STOPPED = range(5)
 JOB_INIT, JOB_QUEUED, JOB_RUNNING, JOB_FINISHED, JOB_FAILED = range(5)
 FLOAT32, INT32, FLOAT16, BFLOAT16 = 0, 1, 2, 3
 SUM = 0
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    L = _kernel_lib()
-    if not _bound:
-        vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
-        L.sml_context_start.restype = i32
-        L.sml_context_start.argtypes = [ctypes.c_char_p]
-        L.sml_context_stop.restype = i32
-        L.sml_context_state.restype = i32
-        L.sml_context_last_error.restype = ctypes.c_char_p
-        L.sml_context_config.restype = ctypes.c_char_p
-        L.sml_allreduce_async.restype = i32
-        L.sml_allreduce_async.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(vp)]
-        L.sml_allreduce.restype = i32
-        L.sml_allreduce.argtypes = [vp, vp, u64, i32, i32]
-        L.sml_wait_for_all_jobs.restype = i32
-        L.sml_job_wait.restype = i32
-        L.sml_job_wait.argtypes = [vp]
-        L.sml_job_status.restype = i32
-        L.sml_job_status.argtypes = [vp]
-        L.sml_job_id.restype = u64
-        L.sml_job_id.argtypes = [vp]
-        L.sml_job_release.argtypes = [vp]
-        L.sml_context_stats.restype = i32
-        L.sml_context_stats.argtypes = [vp]
-        L.sml_context_batch_stats.restype = i32
-        L.sml_context_batch_stats.argtypes = [vp]
-        L.sml_ppp_per_ltu_calls.restype = i32
-        L.sml_ppp_per_ltu_calls.argtypes = [ctypes.c_char_p]
-        _bound = True
-    return L
 
 
 class ContextError(RuntimeError):
@@ -57,7 +22,7 @@ class ContextError(RuntimeError):
 
 def _ok(rc, what):
     if rc != 0:
-        raise ContextError(f"{what} failed ({rc}): {_lib().sml_context_last_error().decode()}")
+        raise ContextError(f"{what} failed ({rc}): {lib().sml_context_last_error().decode()}")
 
 
 def make_config(**kw) -> str:
@@ -85,19 +50,19 @@ def make_config(**kw) -> str:
 
 
 def start(config_ini: str | None = None):
-    _ok(_lib().sml_context_start(None if config_ini is None else config_ini.encode()), "sml_context_start")
+    _ok(lib().sml_context_start(None if config_ini is None else config_ini.encode()), "sml_context_start")
 
 
 def stop():
-    _ok(_lib().sml_context_stop(), "sml_context_stop")
+    _ok(lib().sml_context_stop(), "sml_context_stop")
 
 
 def state() -> int:
-    return _lib().sml_context_state()
+    return lib().sml_context_state()
 
 
 def config_text() -> str:
-    return _lib().sml_context_config().decode()
+    return lib().sml_context_config().decode()
 
 
 def _ptr(t):
@@ -125,18 +90,18 @@ class Job:
 
     @property
     def id(self) -> int:
-        return int(_lib().sml_job_id(self._h))
+        return int(lib().sml_job_id(self._h))
 
     def status(self) -> int:
-        return _lib().sml_job_status(self._h)
+        return lib().sml_job_status(self._h)
 
     def wait(self):
-        _ok(_lib().sml_job_wait(self._h), "sml_job_wait")
+        _ok(lib().sml_job_wait(self._h), "sml_job_wait")
         return self
 
     def __del__(self):
         if getattr(self, "_h", None):
-            _lib().sml_job_release(self._h)
+            lib().sml_job_release(self._h)
             self._h = None
 
 
@@ -167,7 +132,7 @@ def allreduce_async(inp, out=None, numel: int | None = None) -> Job:
     n = inp.numel() if numel is None and hasattr(inp, "numel") and callable(inp.numel) else (
         inp.size if numel is None else numel)
     h = ctypes.c_void_p()
-    _ok(_lib().sml_allreduce_async(_ptr(inp), _ptr(out), n, _dtype_of(inp), SUM, ctypes.byref(h)),
+    _ok(lib().sml_allreduce_async(_ptr(inp), _ptr(out), n, _dtype_of(inp), SUM, ctypes.byref(h)),
         "sml_allreduce_async")
     return Job(h)
 
@@ -177,12 +142,12 @@ def allreduce(inp, out=None):
 
 
 def wait_for_all_jobs():
-    _ok(_lib().sml_wait_for_all_jobs(), "sml_wait_for_all_jobs")
+    _ok(lib().sml_wait_for_all_jobs(), "sml_wait_for_all_jobs")
 
 
 def stats() -> dict:
     arr = (ctypes.c_uint64 * 5)()
-    _ok(_lib().sml_context_stats(ctypes.cast(arr, ctypes.c_void_p)), "sml_context_stats")
+    _ok(lib().sml_context_stats(ctypes.cast(arr, ctypes.c_void_p)), "sml_context_stats")
     return dict(zip(("jobs_submitted", "jobs_finished", "numel_submitted", "slices", "packets"), list(arr)))
 
 
@@ -191,7 +156,7 @@ def batch_stats() -> dict:
     batch worker issued, the job slices they carried, and the job slices it
     ran one by one; all 0 on the threaded path."""
     arr = (ctypes.c_uint64 * 3)()
-    _ok(_lib().sml_context_batch_stats(ctypes.cast(arr, ctypes.c_void_p)), "sml_context_batch_stats")
+    _ok(lib().sml_context_batch_stats(ctypes.cast(arr, ctypes.c_void_p)), "sml_context_batch_stats")
     return dict(zip(("launches", "batched_slices", "single_slices"), list(arr)))
 
 
@@ -199,6 +164,6 @@ def ppp_per_ltu_calls(name: str) -> bool:
     """Whether the prepostprocessor `name` takes per-packet PreprocessSingle /
     PostprocessSingle calls (sml_ppp_per_ltu_calls); ContextError for a name
     the factory rejects."""
-    rc = _lib().sml_ppp_per_ltu_calls(name.encode())
+    rc = lib().sml_ppp_per_ltu_calls(name.encode())
     _ok(min(rc, 0), "sml_ppp_per_ltu_calls")
     return rc == 1

@@ -16,9 +16,9 @@ from __future__ import annotations
 import ctypes
 import os
 
-from . import _HERE
+from .abi import PKG_DIR
 
-PLUGIN_PATH = os.path.join(_HERE, "librccl-net-switchml.so")
+PLUGIN_PATH = os.path.join(PKG_DIR, "librccl-net-switchml.so")
 
 R = ctypes.c_int
 vp = ctypes.c_void_p

@@ -39,8 +39,9 @@ import time
 import torch
 import torch.distributed as dist
 
-from . import (FLAG_PEER_PLANES, _check, bswap_i32, exponents, lib, num_blocks, quantize_pack,
-               release_to_peers, switch_aggregate)
+from . import (FLAG_PEER_PLANES, bswap_i32, exponents, lib, num_blocks, quantize_pack, release_to_peers,
+               switch_aggregate)
+from .abi import call
 
 
 def shard_blocks(num_blocks: int, world: int, rank: int) -> tuple[int, int]:
@@ -52,10 +53,9 @@ def shard_blocks(num_blocks: int, world: int, rank: int) -> tuple[int, int]:
 
 
 def _handle_of(t: torch.Tensor):
-    L = lib()
-    buf = (ctypes.c_uint8 * L.sml_ipc_handle_bytes())()
+    buf = (ctypes.c_uint8 * lib().sml_ipc_handle_bytes())()
     off = ctypes.c_uint64()
-    _check("sml_ipc_get_handle", L.sml_ipc_get_handle(ctypes.c_void_p(t.data_ptr()), buf, ctypes.byref(off)))
+    call("sml_ipc_get_handle", ctypes.c_void_p(t.data_ptr()), buf, ctypes.byref(off))
     return bytes(buf), off.value
 
 
@@ -63,16 +63,15 @@ class _PeerPlane:
     """A peer's int32 plane mapped into this process (a raw device pointer)."""
 
     def __init__(self, handle: bytes, offset: int):
-        L = lib()
         buf = (ctypes.c_uint8 * len(handle)).from_buffer_copy(handle)
         base = ctypes.c_void_p()
-        _check("sml_ipc_open_handle", L.sml_ipc_open_handle(buf, ctypes.byref(base)))
+        call("sml_ipc_open_handle", buf, ctypes.byref(base))
         self.base = base.value
         self.ptr = base.value + offset
 
     def close(self):
         if self.base:
-            _check("sml_ipc_close_handle", lib().sml_ipc_close_handle(ctypes.c_void_p(self.base)))
+            call("sml_ipc_close_handle", ctypes.c_void_p(self.base))
             self.base = None
 
 

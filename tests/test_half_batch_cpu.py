@@ -125,7 +125,7 @@ def test_batch_stats_read_zero_after_a_bypass_context_has_run():
         C.wait_for_all_jobs()
         assert C.stats()["jobs_finished"] == 1
         assert C.batch_stats() == {"launches": 0, "batched_slices": 0, "single_slices": 0}
-        assert C._lib().sml_context_batch_stats(None) != 0
+        assert C.lib().sml_context_batch_stats(None) != 0
     finally:
         if C.state() == C.RUNNING:
             C.stop()

@@ -209,9 +209,9 @@ def test_client_data_type_sizes_and_wire_geometry():
             C.start(C.make_config(prepostprocessor="bypass", num_worker_threads=T, packet_numel=P,
                                   max_outstanding_packets=255, bandwidth=0))
             x = np.zeros(numel, dtype=np.uint16)
-            rc = C._lib().sml_allreduce(ctypes.c_void_p(x.ctypes.data), ctypes.c_void_p(x.ctypes.data), numel, dt,
+            rc = C.lib().sml_allreduce(ctypes.c_void_p(x.ctypes.data), ctypes.c_void_p(x.ctypes.data), numel, dt,
                                         C.SUM)
-            assert rc == 0, C._lib().sml_context_last_error()
+            assert rc == 0, C.lib().sml_context_last_error()
             C.wait_for_all_jobs()      # the finished-jobs counter follows the job's own wake-up
             st = C.stats()
             expect = sum(O.num_blocks(O.slice_geometry(numel, T, t)[1], P) for t in range(T))
@@ -223,9 +223,9 @@ def test_client_data_type_sizes_and_wire_geometry():
         h = np.zeros(777, dtype=np.float16)
         assert C._dtype_of(h) == C.FLOAT16
         assert C.allreduce(h).status() == C.JOB_FINISHED
-        assert C._lib().sml_allreduce(ctypes.c_void_p(h.ctypes.data), ctypes.c_void_p(h.ctypes.data), 777, 4,
+        assert C.lib().sml_allreduce(ctypes.c_void_p(h.ctypes.data), ctypes.c_void_p(h.ctypes.data), 777, 4,
                                       C.SUM) != 0
-        assert C._lib().sml_allreduce(ctypes.c_void_p(h.ctypes.data), ctypes.c_void_p(h.ctypes.data), 777, -1,
+        assert C.lib().sml_allreduce(ctypes.c_void_p(h.ctypes.data), ctypes.c_void_p(h.ctypes.data), 777, -1,
                                       C.SUM) != 0
     finally:
         if C.state() == C.RUNNING:

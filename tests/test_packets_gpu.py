@@ -164,6 +164,26 @@ def test_burst_int32_and_argument_checks(cuda):
 
 
 @pytest.mark.gpu
+def test_burst_error_names_the_entry_point_that_was_called(cuda):
+    """The three burst wrappers go through the sml_*_burst_typed entry points,
+    and a refused burst says so: packet_numel = 100 is no packet size, which
+    every one of them answers before any launch."""
+    import torch
+    s = sw()
+    x = torch.zeros(400, device=cuda)
+    o = torch.zeros_like(x)
+    recv = torch.zeros(4, dtype=torch.int8, device=cuda)
+    ring = torch.zeros(256, dtype=torch.int32, device=cuda)
+    ex = torch.zeros(2, dtype=torch.uint8, device=cuda)
+    bt = s.packet_burst(x, o, 100, 1, 1, recv, [0], [ring.data_ptr()], [ex.data_ptr()])
+    for fn in (s.preprocess_burst, s.postprocess_burst, s.exchange_burst):
+        with pytest.raises(s.SwitchMLError) as err:
+            fn(bt)
+        assert err.value.status == s.SML_ERR_UNSUPPORTED
+        assert str(err.value).startswith(f"sml_{fn.__name__}_typed failed: "), str(err.value)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("W,Q,ring", [(1, 16, "pinned"), (3, 16, "device"), (2, 5, "pinned")])
 def test_rdma_message_loop_with_immediate_words(cuda, W, Q, ring):
     """The RDMA worker's loop (rdma_worker_thread.cc:205-262, 330-356) through
