@@ -16,7 +16,9 @@
 //   (PreprocessBurst, then PostprocessReuseBurst per ring pass), with the
 //   ring and the extra-info slots in two separate hipHostRegister'd
 //   allocations — a NIC pool whose device addresses need not equal its host
-//   addresses, and whose extras are another registration.
+//   addresses, and whose extras are another registration.  Where
+//   the runtime refuses to register memory the process already owns, the two
+//   pools are two separate hipHostMalloc'd allocations.
 // Exit 0: done; 3: per-packet calls refused (message on stdout) — at setup,
 // before any packet, when the configured name takes only the bulk / burst
 // hooks (PrePostProcessor::PerLtuCalls, what a packet-driven backend asks at
@@ -96,15 +98,29 @@ int main(int argc, char** argv) {
             reg_ring = static_cast<int32_t*>(std::aligned_alloc(4096, batch_max * P * 4));
             reg_extra = static_cast<uint8_t*>(std::aligned_alloc(4096, 4096));
             if (!reg_ring || !reg_extra) throw SwitchMLFatal("aligned_alloc");
-            ok(hipHostRegister(reg_ring, batch_max * P * 4, hipHostRegisterMapped), "hipHostRegister");
-            ok(hipHostRegister(reg_extra, 4096, hipHostRegisterMapped), "hipHostRegister");
-            ring = reg_ring;
-            extra = reg_extra;
+            const hipError_t e = hipHostRegister(reg_ring, batch_max * P * 4, hipHostRegisterMapped);
+            if (e == hipSuccess) {
+                ring = reg_ring;
+                ok(hipHostRegister(reg_extra, 4096, hipHostRegisterMapped), "hipHostRegister");
+                extra = reg_extra;
+            } else {
+                // a runtime that cannot pin memory the process already owns (a
+                // virtual machine's GPU): the two pools are two pinned
+                // allocations instead.  The refusal is sticky: cleared here, or
+                // the next launch would report it.
+                (void)hipGetLastError();
+                printf("hipHostRegister: %s; the pools are hipHostMalloc'd\n", hipGetErrorString(e));
+                std::free(reg_ring);
+                std::free(reg_extra);
+                reg_ring = nullptr;
+                reg_extra = nullptr;
+                ok(hipHostMalloc(&ring, batch_max * P * 4, hipHostMallocMapped), "hipHostMalloc");
+                ok(hipHostMalloc(&extra, 4096, hipHostMallocMapped), "hipHostMalloc");
+            }
             void *dr = nullptr, *dx = nullptr;
-            ok(hipHostGetDevicePointer(&dr, reg_ring, 0), "hipHostGetDevicePointer");
-            ok(hipHostGetDevicePointer(&dx, reg_extra, 0), "hipHostGetDevicePointer");
-            printf("registered ring host %p device %p, extras host %p device %p\n", (void*)reg_ring, dr,
-                   (void*)reg_extra, dx);
+            ok(hipHostGetDevicePointer(&dr, ring, 0), "hipHostGetDevicePointer");
+            ok(hipHostGetDevicePointer(&dx, extra, 0), "hipHostGetDevicePointer");
+            printf("ring host %p device %p, extras host %p device %p\n", (void*)ring, dr, (void*)extra, dx);
         }
         auto ppp = PrePostProcessor::CreateInstance(cfg, 0, P * 4, batch_max);
         JobSlice js{nullptr, Tensor{d_in, d_out, numel, FLOAT32}};

@@ -83,8 +83,10 @@ def test_burst_hooks_over_registered_pools_are_exact(cuda, tmp_path, name):
     """the burst hooks over a NIC-like pool — ring and extra-info
     slots in two separate hipHostRegister'd allocations, whose device
     addresses may differ from their host addresses and from each other's
-    offset — translate every buffer by its own registration.  The reference
-    name takes the burst hooks (only its per-packet calls are refused)."""
+    offset — translate every buffer by its own registration.  Where the
+    runtime refuses hipHostRegister the worker takes two separate
+    hipHostMalloc'd pools instead.  The reference name takes the burst hooks
+    (only its per-packet calls are refused)."""
     out = tmp_path / "o.f32"
     numel = 70_001
     r = subprocess.run([BIN, name, str(numel), str(out), "burst-registered"], capture_output=True, text=True,
