@@ -759,6 +759,10 @@ sml_status_t sml_frame_gather(const void* const* sets, uint32_t num_sets, uint64
                               const uint32_t* d_set, const uint64_t* d_index, uint64_t n, uint32_t packet_numel,
                               void* dst, uint64_t dst_stride, uint64_t* d_skipped, void* stream);
 
+/* The switch's side of the RDMA messages — sml_rdma_switch, its state and its
+ * completion record — is declared in switchml_rdma_switch.h, which this header
+ * includes at its end: the same slot pool over landed messages (F4 below). */
+
 /* ncclUint8 buckets of the CollNet plugin (switchml_plugin.cc:318-337,
  * 370-378: "SwitchML does not really support uint8"): each byte widened to an
  * int32 for the INT32 all-reduce, and the summed words narrowed back (mod
@@ -847,5 +851,7 @@ uint64_t sml_set_payload_nt_threshold(uint64_t bytes);
 #ifdef __cplusplus
 }
 #endif
+
+#include "switchml_rdma_switch.h"
 
 #endif /* SWITCHML_HIP_H_ */

@@ -8,7 +8,7 @@ fallback: if the HIP library is missing or the tensor is not on the GPU, the
 call raises.
 
 This file only re-exports: abi.py owns the C ABI, glue.py the torch side, and
-planes, switch, packets, frames, frame_switch and knobs one subsystem's
+planes, switch, packets, frames, frame_switch, rdma_switch and knobs one subsystem's
 wrappers each.  Importing it imports neither torch nor numpy and loads no library.
 """
 from .abi import (BFLOAT16, BURST_EXCHANGE, BURST_POST, BURST_PRE, FLAG_PAYLOAD_LE, FLAG_PEER_PLANES,
@@ -16,8 +16,8 @@ from .abi import (BFLOAT16, BURST_EXCHANGE, BURST_POST, BURST_PRE, FLAG_PAYLOAD_
                   MAX_BATCH_SLICES, MAX_BURST, MAX_FRAME_SWITCH_SLOTS, MAX_FRAME_SWITCH_WORKERS, MAX_SWITCH_WORKERS,
                   PACKET_NUMELS, SML_ERR_ALIGNMENT, SML_ERR_HIP, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_OK,
                   VERDICT_BROADCAST, VERDICT_CONSUMED, VERDICT_DEFERRED, VERDICT_IGNORED, VERDICT_RETRANSMIT,
-                  FrameParams, FrameSwitchParams, PacketBurst, Slice, SwitchMLError, SwitchWorker, TypedSlice,
-                  header_symbols, lib)
+                  FrameParams, FrameSwitchParams, PacketBurst, RdmaArrival, RdmaSwitchParams, Slice, SwitchMLError,
+                  SwitchWorker, TypedSlice, header_symbols, lib)
 from .frame_switch import FrameSwitch, frame_switch_params, gather_frames
 from .frames import (RxSlice, RxSliceInt32, dequantize_frames, frame_bytes, frame_params, pack_frames_int32,
                      quantize_pack_frames, rdma_imm, unpack_frames_int32)
@@ -27,5 +27,6 @@ from .packets import BurstServer, exchange_burst, packet_burst, postprocess_burs
 from .planes import (bswap_i32, dequantize, exponents, fifo_slice, loopback_aggregate, num_blocks, quantize_pack,
                      quantize_pack_launcher, roundtrip_loopback, roundtrip_loopback_batch, scale_lut,
                      scale_lut_device, shard_quantize_pack)
+from .rdma_switch import RdmaSwitch, rdma_rkey
 from .switch import (copy_segments, copy_segments_typed, copy_words, narrow_i32_u8, release_to_peers,
                      switch_aggregate, switch_exps, widen_u8_i32)

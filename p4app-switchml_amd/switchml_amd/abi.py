@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libswitchml_hip.so")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(PKG_DIR)), "include")
 HEADER_PATH = os.path.join(_INCLUDE, "switchml_hip.h")
 CLIENT_HEADER_PATH = os.path.join(_INCLUDE, "switchml_client.h")
+RDMA_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_switch.h")   # included by switchml_hip.h
 
 # sml_status_t
 SML_OK, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_ERR_ALIGNMENT, SML_ERR_HIP = range(5)
@@ -80,6 +81,16 @@ class FrameSwitchParams(ctypes.Structure):
     """sml_frame_switch_params (include/switchml_hip.h)."""
     _fields_ = [("switch_mac", u8 * 6), ("switch_ip_be", u32), ("num_workers", u16), ("num_slots", u32),
                 ("packet_numel", u32), ("workers", SwitchWorker * MAX_FRAME_SWITCH_WORKERS)]
+
+
+class RdmaArrival(ctypes.Structure):
+    """sml_rdma_arrival (include/switchml_rdma_switch.h): one landed message's completion record."""
+    _fields_ = [("worker", u32), ("rkey", u32), ("imm", u32), ("src", u32), ("addr", u64)]
+
+
+class RdmaSwitchParams(ctypes.Structure):
+    """sml_rdma_switch_params (include/switchml_rdma_switch.h)."""
+    _fields_ = [("num_workers", u16), ("num_slots", u32), ("msg_numel", u32), ("pkts_per_msg", u32)]
 
 
 _burst, _frame, _switch = ptr(PacketBurst), ptr(FrameParams), ptr(FrameSwitchParams)
@@ -172,6 +183,14 @@ SIGNATURES = {
     "sml_ppp_per_ltu_calls": (i32, [cstr]),
 }
 
+# include/switchml_rdma_switch.h, the part of the ABI switchml_hip.h includes: a table of its own,
+# held to that header as SIGNATURES is to the other two (tests/test_rdma_switch_cpu.py)
+RDMA_SWITCH_SIGNATURES = {
+    "sml_rdma_switch_state_bytes": (u64, [u32, u32]),
+    "sml_rdma_switch_reset": (i32, [vp, u32, u32, vp]),
+    "sml_rdma_switch": (i32, [ptr(RdmaSwitchParams), vp, u64, vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
+}
+
 _lib = None
 
 
@@ -184,7 +203,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} not found — build it with `make -C p4app-switchml_amd` "
                           "(or __graft_entry__.build()); there is no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

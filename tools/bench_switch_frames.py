@@ -22,7 +22,9 @@ the sum of its slot's payloads.
 and behind the switch call, beside sml_stream_copy of its own algorithmic bytes
 (main_deliver below); --deliver-trace: a few untimed calls of those arms, to
 run under rocprofv3 --kernel-trace.
-Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace"""
+--rdma: the RDMA switch (sml_rdma_switch) on the same two shapes, beside the
+copy and the frame path (main_rdma below).
+Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace | --rdma [OUT.json]"""
 import json
 import os
 import statistics
@@ -272,7 +274,100 @@ def main_deliver(out_path=None, rounds=7, W=8, P=256, trace_only=False):
     return 0
 
 
+def main_rdma(out_path=None, rounds=7, W=8, M=256):
+    """The RDMA switch (sml_rdma_switch: claim, verdicts, apply + results) on
+    the same two shapes, a message per (slot, worker), every call completing
+    its slots and writing W results per slot: beside sml_stream_copy of its own
+    algorithmic bytes (every message and record read once, the slots' words
+    written once, W S results written) and beside the frame path, sml_frame_switch
+    + sml_frame_switch_deliver at P = M, in the same process."""
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream()
+    fb = sw.frame_bytes(M)
+    arms, meta = {}, {}
+    for name, (S, nbuf, reps) in {"window": (256, 2, 200), "batch": (16384, 4, 10)}.items():
+        F = S * W
+        rs = sw.RdmaSwitch(W, S, M, 1, device=dev)
+        landing = [torch.empty((F, 4 * M), dtype=torch.uint8, device=dev).random_(0, 256) for _ in range(nbuf)]
+        rx = torch.zeros((W, S * 4 * M), dtype=torch.uint8, device=dev)
+        recs = []
+        for k in range(nbuf):                                # message slot * W + w, in a seeded arrival order
+            order = np.random.default_rng(80 + k).permutation(F)
+            a = np.zeros(F, dtype=np.dtype(sw.rdma_switch.ARRIVAL_FIELDS))
+            a["worker"], a["rkey"], a["imm"], a["src"] = order % W, (order // W) << 1 | (k & 1), order // W, order
+            a["addr"] = (order // W) * 4 * M
+            recs.append(torch.from_numpy(a.view(np.uint8)).to(dev))
+        vd = torch.empty(F, dtype=torch.uint8, device=dev)
+        imm = torch.zeros(F, dtype=torch.int32, device=dev)
+        # checked before anything is timed: every slot completes, every region holds slot 0's wrapping sum
+        rs.step(recs[0], landing[0], rx, verdict=vd, out_imm=imm)
+        torch.cuda.synchronize()
+        assert rs.counts.tolist() == [S * (W - 1), S, 0, 0, 0, 0], rs.counts.tolist()
+        want = landing[0][:W].cpu().numpy().view(">u4").astype(np.uint32).sum(axis=0, dtype=np.uint32)
+        for u in (0, W - 1):
+            assert np.array_equal(rx[u, :4 * M].cpu().numpy().view(">u4").astype(np.uint32), want)
+        rs.reset()
+
+        fs = sw.FrameSwitch(WORKERS, S, M, device=dev)
+        sets = [frame_set(S, W, M, k & 1, 60 + k, dev) for k in range(nbuf)]
+        out = torch.zeros(F * fb, dtype=torch.uint8, device=dev)
+        fvd = torch.empty(F, dtype=torch.uint8, device=dev)
+        rings = torch.zeros((W, (reps + 4) * S, fb), dtype=torch.uint8, device=dev)
+
+        def rdma(k, rs=rs, recs=recs, landing=landing, rx=rx, vd=vd, imm=imm, nbuf=nbuf):
+            rs.step(recs[k % nbuf], landing[k % nbuf], rx, verdict=vd, out_imm=imm, stream=st)
+
+        def frames(k, fs=fs, sets=sets, nbuf=nbuf, out=out, fvd=fvd, F=F, rings=rings):
+            fs(sets[k % nbuf][0], F, out=out, verdict=fvd, stream=st)
+            fs.deliver(out, fvd, F, rings=rings, stream=st)
+
+        alg = F * 4 * M + 24 * F + S * 4 * M + W * S * 4 * M
+        half = (alg // 2 + 4095) // 4096 * 4096
+        src = [torch.empty(half, dtype=torch.uint8, device=dev).random_(0, 256) for _ in range(nbuf)]
+        dst = [torch.empty(half, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+
+        def copy(k, src=src, dst=dst, nbuf=nbuf):
+            sw.stream_copy(src[k % nbuf], dst[k % nbuf], stream=st)
+
+        arms[name + "_rdma_switch"] = (rdma, reps, None)
+        arms[name + "_frame_switch_deliver"] = (frames, reps, fs)
+        arms[name + "_stream_copy"] = (copy, reps, None)
+        meta[name] = dict(messages_per_call=F, results_written=W * S, algorithmic_bytes=alg, copy_bytes_moved=2 * half)
+    times = {name: [] for name in arms}
+    step = [0]
+    for _ in range(rounds):
+        for name, (fn, reps, fs) in arms.items():
+            assert step[0] % 2 == 0 and reps % 2 == 0            # a switch's calls alternate its slots' sets
+            if fs is not None:
+                fs.reset_rings()
+            times[name].append(timed(fn, st, reps, step))
+    res = {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+           for name, v in times.items()}
+    for name, m in meta.items():
+        us, cp = (statistics.median(times[name + a]) for a in ("_rdma_switch", "_stream_copy"))
+        fr = statistics.median(times[name + "_frame_switch_deliver"])
+        res[name + "_rdma_switch"].update(m, TBps_algorithmic=round(m["algorithmic_bytes"] / us / 1e6, 3),
+                                          time_over_stream_copy=round(us / cp, 3),
+                                          frame_path_over_rdma=round(fr / us, 3))
+        res[name + "_stream_copy"].update(TBps=round(m["copy_bytes_moved"] / cp / 1e6, 3))
+    text = json.dumps({
+        "what": f"side measurement (not bench.py's headline): sml_rdma_switch, W={W}, msg_numel={M}, pkts_per_msg=1, "
+                f"on bench_switch_frames.py's two shapes (window: 256 slots, 2048 arrivals; batch: 16384 slots, "
+                f"131072 arrivals; every call completes its slots and writes W results per slot), beside "
+                f"sml_stream_copy of its algorithmic bytes and sml_frame_switch + sml_frame_switch_deliver at P={M} "
+                f"in the same process; {rounds} interleaved rounds, medians with the rounds' min-max, HIP events; "
+                f"nothing here was measured before this file was written",
+        "device": torch.cuda.get_device_name(0), "arms": res}, indent=1)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--rdma":
+        sys.exit(main_rdma(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--deliver":
         sys.exit(main_deliver(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--deliver-trace":
