@@ -8,8 +8,8 @@ fallback: if the HIP library is missing or the tensor is not on the GPU, the
 call raises.
 
 This file only re-exports: abi.py owns the C ABI, glue.py the torch side, and
-planes, switch, packets, frames, frame_switch, rdma_switch and knobs one subsystem's
-wrappers each.  Importing it imports neither torch nor numpy and loads no library.
+planes, switch, packets, frames, frame_switch, rdma_switch, rdma_worker and knobs
+one subsystem's wrappers each.  Importing it imports neither torch nor numpy and loads no library.
 """
 from .abi import (BFLOAT16, BURST_EXCHANGE, BURST_POST, BURST_PRE, FLAG_PAYLOAD_LE, FLAG_PEER_PLANES,
                   FLAG_PROCESS_PACKET, FLAG_ROUND_RNE, FLOAT16, FLOAT32, HEADER_PATH, INT32, LIB_PATH,
@@ -18,6 +18,8 @@ from .abi import (BFLOAT16, BURST_EXCHANGE, BURST_POST, BURST_PRE, FLAG_PAYLOAD_
                   VERDICT_BROADCAST, VERDICT_CONSUMED, VERDICT_DEFERRED, VERDICT_IGNORED, VERDICT_RETRANSMIT,
                   FrameParams, FrameSwitchParams, PacketBurst, RdmaArrival, RdmaSwitchParams, Slice, SwitchMLError,
                   SwitchWorker, TypedSlice, header_symbols, lib)
+from .abi import (RDMA_WORKER_FINISHED, RDMA_WORKER_IGNORED, RDMA_WORKER_POSTED, RDMA_WORKER_WRONG, RdmaCompletion,
+                  RdmaWorkerParams)
 from .frame_switch import FrameSwitch, frame_switch_params, gather_frames
 from .frames import (RxSlice, RxSliceInt32, dequantize_frames, frame_bytes, frame_params, pack_frames_int32,
                      quantize_pack_frames, rdma_imm, unpack_frames_int32)
@@ -28,5 +30,6 @@ from .planes import (bswap_i32, dequantize, exponents, fifo_slice, loopback_aggr
                      quantize_pack_launcher, roundtrip_loopback, roundtrip_loopback_batch, scale_lut,
                      scale_lut_device, shard_quantize_pack)
 from .rdma_switch import RdmaSwitch, rdma_rkey
+from .rdma_worker import RdmaWorker
 from .switch import (copy_segments, copy_segments_typed, copy_words, narrow_i32_u8, release_to_peers,
                      switch_aggregate, switch_exps, widen_u8_i32)

@@ -19,6 +19,7 @@ _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(PKG_DIR)), "include")
 HEADER_PATH = os.path.join(_INCLUDE, "switchml_hip.h")
 CLIENT_HEADER_PATH = os.path.join(_INCLUDE, "switchml_client.h")
 RDMA_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_switch.h")   # included by switchml_hip.h
+RDMA_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_worker.h")   # included by switchml_hip.h
 
 # sml_status_t
 SML_OK, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_ERR_ALIGNMENT, SML_ERR_HIP = range(5)
@@ -92,6 +93,20 @@ class RdmaSwitchParams(ctypes.Structure):
     """sml_rdma_switch_params (include/switchml_rdma_switch.h)."""
     _fields_ = [("num_workers", u16), ("num_slots", u32), ("msg_numel", u32), ("pkts_per_msg", u32)]
 
+
+class RdmaCompletion(ctypes.Structure):
+    """sml_rdma_completion (include/switchml_rdma_worker.h): wr_id & 0xFFFF and imm_data of one completion."""
+    _fields_ = [("qpn", u32), ("imm", u32)]
+
+
+class RdmaWorkerParams(ctypes.Structure):
+    """sml_rdma_worker_params (include/switchml_rdma_worker.h)."""
+    _fields_ = [("worker", u32), ("num_workers", u16), ("data_type", u16), ("msg_numel", u32), ("pkts_per_msg", u32),
+                ("num_qps", u32), ("first_slot", u32), ("src_base", u32), ("flags", u32)]
+
+
+# sml_rdma_worker_poll's verdict per completion
+RDMA_WORKER_WRONG, RDMA_WORKER_POSTED, RDMA_WORKER_FINISHED, RDMA_WORKER_IGNORED = range(4)
 
 _burst, _frame, _switch = ptr(PacketBurst), ptr(FrameParams), ptr(FrameSwitchParams)
 
@@ -191,6 +206,16 @@ RDMA_SWITCH_SIGNATURES = {
     "sml_rdma_switch": (i32, [ptr(RdmaSwitchParams), vp, u64, vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
 }
 
+# include/switchml_rdma_worker.h, likewise (tests/test_rdma_worker_cpu.py)
+_worker = ptr(RdmaWorkerParams)
+RDMA_WORKER_SIGNATURES = {
+    "sml_rdma_worker_state_bytes": (u64, [u32]),
+    "sml_rdma_worker_reset": (i32, [vp, u32, vp]),
+    "sml_rdma_worker_begin": (i32, [_worker, vp, vp, u64, vp, vp, vp, vp]),
+    "sml_rdma_worker_poll": (i32, [_worker, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+    "sml_rdma_worker_resend": (i32, [_worker, vp, u64, vp, vp, vp]),
+}
+
 _lib = None
 
 
@@ -203,7 +228,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} not found — build it with `make -C p4app-switchml_amd` "
                           "(or __graft_entry__.build()); there is no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES, **RDMA_WORKER_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

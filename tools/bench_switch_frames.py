@@ -24,7 +24,10 @@ and behind the switch call, beside sml_stream_copy of its own algorithmic bytes
 run under rocprofv3 --kernel-trace.
 --rdma: the RDMA switch (sml_rdma_switch) on the same two shapes, beside the
 copy and the frame path (main_rdma below).
-Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace | --rdma [OUT.json]"""
+--rdma-worker: the RDMA worker's completion loop (sml_rdma_worker_poll) beside
+the per-packet exchange bursts and the copy (main_rdma_worker below).
+Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace | --rdma [OUT.json]
+       | --rdma-worker [OUT.json]"""
 import json
 import os
 import statistics
@@ -365,7 +368,111 @@ def main_rdma(out_path=None, rounds=7, W=8, M=256):
     return 0
 
 
+def main_rdma_worker(out_path=None, rounds=7, W=8, M=1024, reps=10):
+    """The RDMA worker's completion loop (sml_rdma_worker_poll: judge, accept)
+    at Q = 16384 and Q = 64 queue pairs: FLOAT32, a slice of 4 Q M elements, a
+    timed step = one poll in which every QP accepts a steady-state message
+    (b <= m < B - b: block m - b out, block m in, block m + b's exponent).  A
+    slice has two such polls per QP, so a timing is the two of them between one
+    pair of HIP events, the QP state put back (untimed) before each pair; the
+    other arms are timed the same way: (b) the same messages through
+    ceil(Q / 64) prebuilt sml_exchange_burst launches, the host holding the
+    ids; (c) sml_stream_copy of the poll's algorithmic bytes (20 KiB a message:
+    result read, output written, two slice blocks read, message written; plus
+    its records).  Call time from events, not kernel time."""
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream()
+    arms, meta = {}, {}
+    for name, Q in {"q16384": 16384, "q64": 64}.items():
+        n = 4 * Q * M
+        x = torch.empty(n, dtype=torch.float32, device=dev).normal_()
+        out = torch.empty_like(x)
+        buf = torch.empty(Q * M, dtype=torch.int32, device=dev).random_(-2 ** 31, 2 ** 31 - 1)   # tx is rx
+        wk = sw.RdmaWorker(0, W, Q, M, 4, dtype=torch.float32, device=dev)
+        comps = []
+        for r in range(3):                                   # messages r Q + q: the first batch, then two steady ones
+            c = np.zeros(Q, dtype=np.dtype(sw.rdma_worker.COMPLETION_FIELDS))
+            c["qpn"], c["imm"] = np.arange(Q), ((r * Q + np.arange(Q)) & 0xFFFF) | (3 << 16)
+            comps.append(torch.from_numpy(c.view(np.int64)).to(dev))
+        wk.begin(x, out, buf)
+        verdict, _ = wk.poll(comps[0], buf, buf)
+        assert bool((verdict == sw.RDMA_WORKER_POSTED).all())
+        snap = wk.state.clone()
+        for r in (1, 2):                                     # checked before anything is timed: both polls post
+            assert bool((wk.poll(comps[r], buf, buf)[0] == sw.RDMA_WORKER_POSTED).all())
+
+        recv = torch.full((4 * Q,), 3, dtype=torch.int8, device=dev)
+        immw = torch.zeros(Q, dtype=torch.int32, device=dev)
+        bursts = [[sw.packet_burst(x, out, M, W, Q, recv, list(range(r * Q + q0, r * Q + min(q0 + 64, Q))),
+                                   [buf.data_ptr() + q * 4 * M for q in range(q0, min(q0 + 64, Q))],
+                                   [immw.data_ptr() + 4 * q + 2 for q in range(q0, min(q0 + 64, Q))])
+                   for q0 in range(0, Q, 64)] for r in (1, 2)]
+
+        def poll(r, wk=wk, comps=comps, buf=buf):
+            wk.poll(comps[r], buf, buf, stream=st)
+
+        def burst(r, bursts=bursts):
+            for bt in bursts[r - 1]:
+                sw.exchange_burst(bt, stream=st)
+
+        alg = Q * (5 * 4 * M + 8 + 24 + 1 + 2 * 32)
+        half = (alg // 2 + 4095) // 4096 * 4096
+        src = torch.empty(half, dtype=torch.uint8, device=dev).random_(0, 256)
+        dst = torch.empty(half, dtype=torch.uint8, device=dev)
+
+        def copy(r, src=src, dst=dst):
+            sw.stream_copy(src, dst, stream=st)
+
+        restore = lambda wk=wk, snap=snap: wk.state.copy_(snap)                       # noqa: E731
+        arms[name + "_worker_poll"] = (poll, restore)
+        arms[name + "_exchange_bursts"] = (burst, None)
+        arms[name + "_stream_copy"] = (copy, None)
+        meta[name] = dict(messages_per_call=Q, algorithmic_bytes=alg, copy_bytes_moved=2 * half,
+                          burst_launches_per_call=(Q + 63) // 64, worker_launches_per_call=2)
+
+    def pair(fn, restore):
+        if restore:
+            restore()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(st)
+        fn(1)
+        fn(2)
+        b.record(st)
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / 2 * 1e3
+
+    times = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, (fn, restore) in arms.items():
+            pair(fn, restore)                                                         # warmed
+            times[name].append(statistics.median(pair(fn, restore) for _ in range(reps)))
+    res = {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+           for name, v in times.items()}
+    for name, m in meta.items():
+        us, bu, cp = (statistics.median(times[name + a]) for a in ("_worker_poll", "_exchange_bursts", "_stream_copy"))
+        res[name + "_worker_poll"].update(m, TBps_algorithmic=round(m["algorithmic_bytes"] / us / 1e6, 3),
+                                          time_over_stream_copy=round(us / cp, 3),
+                                          exchange_bursts_over_worker_poll=round(bu / us, 3))
+        res[name + "_stream_copy"].update(TBps=round(m["copy_bytes_moved"] / cp / 1e6, 3))
+    text = json.dumps({
+        "what": f"side measurement (not bench.py's headline): sml_rdma_worker_poll, FLOAT32, W={W}, msg_numel={M}, a "
+                f"slice of 4 Q M elements, tx == rx in device memory; one call = one poll in which every QP accepts "
+                f"a steady-state message, beside the same messages through ceil(Q / 64) prebuilt sml_exchange_burst "
+                f"launches and sml_stream_copy of the poll's algorithmic bytes, in the same process; a timing = two "
+                f"calls between one pair of HIP events (call time, not kernel time), the median of {reps} such per "
+                f"round, {rounds} interleaved rounds, medians with the rounds' min-max; the buffers are reused "
+                f"between timings (not cold); nothing here was measured before this file was written",
+        "device": torch.cuda.get_device_name(0), "arms": res}, indent=1)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--rdma-worker":
+        sys.exit(main_rdma_worker(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--rdma":
         sys.exit(main_rdma(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--deliver":
