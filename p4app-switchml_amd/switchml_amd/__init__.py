@@ -8,8 +8,8 @@ fallback: if the HIP library is missing or the tensor is not on the GPU, the
 call raises.
 
 This file only re-exports: abi.py owns the C ABI, glue.py the torch side, and
-planes, switch, packets, frames, frame_switch, rdma_switch, rdma_worker and knobs
-one subsystem's wrappers each.  Importing it imports neither torch nor numpy and loads no library.
+planes, switch, packets, frames, frame_switch, frame_worker, rdma_switch, rdma_worker and
+knobs one subsystem's wrappers each.  Importing it imports neither torch nor numpy and loads no library.
 """
 from .abi import (BFLOAT16, BURST_EXCHANGE, BURST_POST, BURST_PRE, FLAG_PAYLOAD_LE, FLAG_PEER_PLANES,
                   FLAG_PROCESS_PACKET, FLAG_ROUND_RNE, FLOAT16, FLOAT32, HEADER_PATH, INT32, LIB_PATH,
@@ -20,7 +20,10 @@ from .abi import (BFLOAT16, BURST_EXCHANGE, BURST_POST, BURST_PRE, FLAG_PAYLOAD_
                   SwitchWorker, TypedSlice, header_symbols, lib)
 from .abi import (RDMA_WORKER_FINISHED, RDMA_WORKER_IGNORED, RDMA_WORKER_POSTED, RDMA_WORKER_WRONG, RdmaCompletion,
                   RdmaWorkerParams)
+from .abi import (FRAME_WORKER_FINISHED, FRAME_WORKER_IGNORED, FRAME_WORKER_NONE, FRAME_WORKER_POSTED,
+                  FRAME_WORKER_WRONG, FrameWorkerParams)
 from .frame_switch import FrameSwitch, frame_switch_params, gather_frames
+from .frame_worker import FrameWorker
 from .frames import (RxSlice, RxSliceInt32, dequantize_frames, frame_bytes, frame_params, pack_frames_int32,
                      quantize_pack_frames, rdma_imm, unpack_frames_int32)
 from .knobs import (debug_stall, set_grid_limit, set_payload_nt_threshold, set_quantize_tile_slices,

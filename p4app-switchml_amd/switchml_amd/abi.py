@@ -20,6 +20,7 @@ HEADER_PATH = os.path.join(_INCLUDE, "switchml_hip.h")
 CLIENT_HEADER_PATH = os.path.join(_INCLUDE, "switchml_client.h")
 RDMA_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_switch.h")   # included by switchml_hip.h
 RDMA_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_worker.h")   # included by switchml_hip.h
+FRAME_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_frame_worker.h")  # included by switchml_hip.h
 
 # sml_status_t
 SML_OK, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_ERR_ALIGNMENT, SML_ERR_HIP = range(5)
@@ -107,6 +108,16 @@ class RdmaWorkerParams(ctypes.Structure):
 
 # sml_rdma_worker_poll's verdict per completion
 RDMA_WORKER_WRONG, RDMA_WORKER_POSTED, RDMA_WORKER_FINISHED, RDMA_WORKER_IGNORED = range(4)
+
+class FrameWorkerParams(ctypes.Structure):
+    """sml_frame_worker_params (include/switchml_frame_worker.h)."""
+    _fields_ = [("frame", FrameParams), ("num_workers", u16), ("data_type", u16), ("packet_numel", u32),
+                ("flags", u32)]
+
+
+# sml_frame_worker_poll's verdict per received frame; a d_sends entry that sends nothing
+FRAME_WORKER_WRONG, FRAME_WORKER_POSTED, FRAME_WORKER_FINISHED, FRAME_WORKER_IGNORED = range(4)
+FRAME_WORKER_NONE = 0xFFFFFFFFFFFFFFFF
 
 _burst, _frame, _switch = ptr(PacketBurst), ptr(FrameParams), ptr(FrameSwitchParams)
 
@@ -216,6 +227,16 @@ RDMA_WORKER_SIGNATURES = {
     "sml_rdma_worker_resend": (i32, [_worker, vp, u64, vp, vp, vp]),
 }
 
+# include/switchml_frame_worker.h, likewise (tests/test_frame_worker_cpu.py)
+_fworker = ptr(FrameWorkerParams)
+FRAME_WORKER_SIGNATURES = {
+    "sml_frame_worker_state_bytes": (u64, [u32]),
+    "sml_frame_worker_reset": (i32, [vp, u32, vp]),
+    "sml_frame_worker_begin": (i32, [_fworker, vp, vp, u64, vp, vp, u64, vp, vp]),
+    "sml_frame_worker_poll": (i32, [_fworker, vp, u64, u64, vp, vp, vp, u64, vp, vp, vp, vp]),
+    "sml_frame_worker_resend": (i32, [_fworker, vp, u64, vp, vp, vp]),
+}
+
 _lib = None
 
 
@@ -228,7 +249,8 @@ def lib():
         raise ImportError(f"{LIB_PATH} not found — build it with `make -C p4app-switchml_amd` "
                           "(or __graft_entry__.build()); there is no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES, **RDMA_WORKER_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES, **RDMA_WORKER_SIGNATURES,
+                                      **FRAME_WORKER_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -26,8 +26,10 @@ run under rocprofv3 --kernel-trace.
 copy and the frame path (main_rdma below).
 --rdma-worker: the RDMA worker's completion loop (sml_rdma_worker_poll) beside
 the per-packet exchange bursts and the copy (main_rdma_worker below).
+--frame-worker: the DPDK worker's receive loop (sml_frame_worker_poll) beside
+the bulk tx + rx pair over as many frames and the copy (main_frame_worker below).
 Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace | --rdma [OUT.json]
-       | --rdma-worker [OUT.json]"""
+       | --rdma-worker [OUT.json] | --frame-worker [OUT.json]"""
 import json
 import os
 import statistics
@@ -470,7 +472,121 @@ def main_rdma_worker(out_path=None, rounds=7, W=8, M=1024, reps=10):
     return 0
 
 
+def main_frame_worker(out_path=None, rounds=7, W=8, P=256, reps=10):
+    """The DPDK worker's receive loop (sml_frame_worker_poll: judge, accept) at
+    Q = 16384 and Q = 64 tx slots: FLOAT32, a slice of 4 Q P elements, a timed
+    step = one poll over Q received frames in which every slot accepts a
+    steady-state packet (b <= p < B - b: block p - b out, block p into frame
+    p + b, block p + b's exponent).  A slice has two such polls per slot, so a
+    timing is the two of them between one pair of HIP events, the slot state put
+    back (untimed) before each pair; the other arms are timed the same way:
+    (b) the route that exists without it for as many frames, one
+    sml_quantize_pack_frames building Q frames (Q / 2 blocks, batch_max Q / 2,
+    global exponents given) plus one sml_dequantize_frames over Q received
+    frames, its rx state cleared (untimed) before each pair; (c)
+    sml_stream_copy of the poll's algorithmic bytes (per frame: the frame read,
+    the output block written, two slice blocks read, the frame written).  Call
+    time from events, not kernel time."""
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream()
+    fb = sw.frame_bytes(P)
+    arms, meta = {}, {}
+    for name, Q in {"q16384": 16384, "q64": 64}.items():
+        n = 4 * Q * P
+        x = torch.empty(n, dtype=torch.float32, device=dev).normal_()
+        out = torch.empty_like(x)
+        prm = sw.frame_params(job_id=5, max_outstanding_pkts=Q)
+        wk = sw.FrameWorker(prm, W, P, dtype=torch.float32, device=dev)
+        tx = torch.zeros(Q * fb, dtype=torch.uint8, device=dev)
+        rings = []
+        for r in range(3):                                   # packets r Q + q: the first batch, then two steady ones
+            hdr = np.zeros((Q, FW.HEADER_BYTES), dtype=np.uint8)
+            FW.put(hdr, FW.JOB, 5)
+            FW.put(hdr, FW.PKT_ID, r * Q + np.arange(Q))
+            FW.put(hdr, FW.EXP, 3)
+            fr = torch.empty((Q, fb), dtype=torch.uint8, device=dev).random_(0, 256)
+            fr[:, :FW.HEADER_BYTES] = torch.from_numpy(hdr).to(dev)
+            rings.append(fr.reshape(-1))
+        wk.begin(x, out, tx)
+        assert bool((wk.poll(rings[0], Q, tx)[0] == sw.FRAME_WORKER_POSTED).all())
+        snap = wk.state.clone()
+        for r in (1, 2):                                     # checked before anything is timed: both polls post
+            assert bool((wk.poll(rings[r], Q, tx)[0] == sw.FRAME_WORKER_POSTED).all())
+
+        xb = x[:Q // 2 * P]
+        gexp = torch.full((Q // 2,), 3, dtype=torch.int8, device=dev)
+        bulk_tx = torch.zeros(Q * fb, dtype=torch.uint8, device=dev)
+        rxs = [sw.RxSlice(Q // 2 * P, P, batch_max=Q // 2, device=dev) for _ in range(2)]
+        bulk_rx = sw.quantize_pack_frames(xb, prm, P, W, batch_max=Q // 2, global_exps=gexp).clone()
+        sw.dequantize_frames(bulk_rx, Q, rxs[0], num_workers=W, job_id=5)
+        torch.cuda.synchronize()
+        assert rxs[0].counts.tolist() == [Q, 0]              # every frame of the bulk pair is accepted too
+
+        def poll(r, wk=wk, rings=rings, tx=tx, Q=Q):
+            wk.poll(rings[r], Q, tx, stream=st)
+
+        def bulk(r, xb=xb, prm=prm, gexp=gexp, bulk_tx=bulk_tx, bulk_rx=bulk_rx, rxs=rxs, Q=Q):
+            sw.quantize_pack_frames(xb, prm, P, W, batch_max=Q // 2, global_exps=gexp, frames=bulk_tx, stream=st)
+            sw.dequantize_frames(bulk_rx, Q, rxs[r - 1], num_workers=W, job_id=5, stream=st)
+
+        alg = Q * (2 * fb + 3 * 4 * P)
+        half = (alg // 2 + 4095) // 4096 * 4096
+        src = torch.empty(half, dtype=torch.uint8, device=dev).random_(0, 256)
+        dst = torch.empty(half, dtype=torch.uint8, device=dev)
+
+        def copy(r, src=src, dst=dst):
+            sw.stream_copy(src, dst, stream=st)
+
+        arms[name + "_worker_poll"] = (poll, lambda wk=wk, snap=snap: wk.state.copy_(snap))
+        arms[name + "_bulk_tx_rx"] = (bulk, lambda rxs=rxs: [rx.reset() for rx in rxs])
+        arms[name + "_stream_copy"] = (copy, None)
+        meta[name] = dict(frames_per_call=Q, algorithmic_bytes=alg, copy_bytes_moved=2 * half,
+                          bulk_launches_per_call=3, worker_launches_per_call=2)
+
+    def pair(fn, restore):
+        if restore:
+            restore()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(st)
+        fn(1)
+        fn(2)
+        b.record(st)
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / 2 * 1e3
+
+    times = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, (fn, restore) in arms.items():
+            pair(fn, restore)                                                         # warmed
+            times[name].append(statistics.median(pair(fn, restore) for _ in range(reps)))
+    res = {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+           for name, v in times.items()}
+    for name, m in meta.items():
+        us, bu, cp = (statistics.median(times[name + a]) for a in ("_worker_poll", "_bulk_tx_rx", "_stream_copy"))
+        res[name + "_worker_poll"].update(m, TBps_algorithmic=round(m["algorithmic_bytes"] / us / 1e6, 3),
+                                          time_over_stream_copy=round(us / cp, 3),
+                                          bulk_tx_rx_over_worker_poll=round(bu / us, 3))
+        res[name + "_stream_copy"].update(TBps=round(m["copy_bytes_moved"] / cp / 1e6, 3))
+    text = json.dumps({
+        "what": f"side measurement (not bench.py's headline): sml_frame_worker_poll, FLOAT32, W={W}, P={P}, a slice of "
+                f"4 Q P elements, tx and rx in device memory; one call = one poll over Q frames in which every slot "
+                f"accepts a steady-state packet, beside one sml_quantize_pack_frames (Q frames built) plus one "
+                f"sml_dequantize_frames (Q frames received) and sml_stream_copy of the poll's algorithmic bytes, in "
+                f"the same process; a timing = two calls between one pair of HIP events (call time, not kernel "
+                f"time), the median of {reps} such per round, {rounds} interleaved rounds, medians with the rounds' "
+                f"min-max; the buffers are reused between timings (not cold); nothing here was measured before this "
+                f"file was written",
+        "device": torch.cuda.get_device_name(0), "arms": res}, indent=1)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--frame-worker":
+        sys.exit(main_frame_worker(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--rdma-worker":
         sys.exit(main_rdma_worker(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--rdma":
