@@ -21,6 +21,7 @@ CLIENT_HEADER_PATH = os.path.join(_INCLUDE, "switchml_client.h")
 RDMA_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_switch.h")   # included by switchml_hip.h
 RDMA_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_worker.h")   # included by switchml_hip.h
 FRAME_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_frame_worker.h")  # included by switchml_hip.h
+MESSAGES_HEADER_PATH = os.path.join(_INCLUDE, "switchml_messages.h")          # included by switchml_hip.h
 
 # sml_status_t
 SML_OK, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_ERR_ALIGNMENT, SML_ERR_HIP = range(5)
@@ -40,6 +41,8 @@ MAX_SWITCH_WORKERS = 16
 MAX_BURST = 64
 MAX_FRAME_SWITCH_WORKERS = 32
 MAX_FRAME_SWITCH_SLOTS = 16384
+# include/switchml_messages.h: a message holds a multiple of the step, up to the maximum
+MSG_NUMEL_STEP, MSG_NUMEL_MAX = 64, 16384
 # sml_frame_switch's verdict per input frame
 VERDICT_CONSUMED, VERDICT_BROADCAST, VERDICT_RETRANSMIT, VERDICT_IGNORED, VERDICT_DEFERRED = range(5)
 # sml_burst_server_submit's op
@@ -237,6 +240,15 @@ FRAME_WORKER_SIGNATURES = {
     "sml_frame_worker_resend": (i32, [_fworker, vp, u64, vp, vp, vp]),
 }
 
+# include/switchml_messages.h, likewise (tests/test_messages_cpu.py)
+MESSAGES_SIGNATURES = {
+    "sml_msg_numel_supported": (i32, [u32]),
+    "sml_msg_exponents": (i32, [vp, i32, u64, u32, vp, vp]),
+    "sml_msg_quantize_pack": (i32, [vp, i32, u64, u32, u16, vp, vp, vp, u32, vp]),
+    "sml_msg_dequantize": (i32, [vp, vp, u64, u32, u16, vp, i32, u32, vp]),
+    "sml_msg_roundtrip_loopback": (i32, [vp, vp, i32, u64, u32, u16, vp, vp, u32, vp]),
+}
+
 _lib = None
 
 
@@ -250,7 +262,7 @@ def lib():
                           "(or __graft_entry__.build()); there is no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES, **RDMA_WORKER_SIGNATURES,
-                                      **FRAME_WORKER_SIGNATURES}.items():
+                                      **FRAME_WORKER_SIGNATURES, **MESSAGES_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
