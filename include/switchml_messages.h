@@ -43,14 +43,19 @@
  * What a caller composes from what exists:
  *   the RDMA immediates of a slice: sml_rdma_imm on the message exponent plane
  *     (sml_msg_exponents or sml_msg_quantize_pack's d_exps_out);
- *   a W-worker switch step: sml_msg_exponents per worker -> sml_switch_exps ->
+ *   the switch such workers talk to: sml_msg_switch (switchml_msg_switch.h),
+ *     sml_rdma_switch's slot pool, worker bitmap, retransmission and receive
+ *     regions for every msg_numel served here and pkts_per_msg up to 256;
+ *   a W-worker switch step on whole planes, without a slot pool:
+ *     sml_msg_exponents per worker -> sml_switch_exps ->
  *     sml_msg_quantize_pack with the global exponents per worker ->
  *     sml_switch_aggregate with d_out = NULL (the payload sum knows no block
  *     size: pass any packet size that divides B*M, such as 64) ->
  *     sml_msg_dequantize.
  * Not served at msg_numel > 1024 (they keep returning SML_ERR_UNSUPPORTED): the
- * per-packet bursts, the batched round trip, the DPDK frames, sml_rdma_switch,
- * the sml_rdma_worker_* calls and the client's config keys. */
+ * per-packet bursts, the batched round trip, the DPDK frames, sml_rdma_switch
+ * itself (its sml_msg_switch twin serves them), the sml_rdma_worker_* calls and
+ * the client's config keys. */
 #ifndef SWITCHML_MESSAGES_H_
 #define SWITCHML_MESSAGES_H_
 

@@ -73,7 +73,9 @@
  * record; a result record joins its slot's list), apply and results (wave per
  * touched slot: the new contributors' messages summed in registers, the
  * registers advanced, and the sum written from registers to the receive
- * regions of the slot's result records). */
+ * regions of the slot's result records).
+ *   Messages of more than 1024 words, and any pkts_per_msg up to 256: the
+ * sml_msg_switch* twins of these three calls (switchml_msg_switch.h). */
 #ifndef SWITCHML_RDMA_SWITCH_H_
 #define SWITCHML_RDMA_SWITCH_H_
 

@@ -72,6 +72,11 @@ struct RsArgs {
     uint32_t S, W;
     uint32_t ppm_shift;             // log2(pkts_per_msg)
     uint32_t fits;                  // rx_bytes holds a message at all
+    // sml_msg_switch only: any pkts_per_msg, and a message as items of slices
+    uint32_t ppm;                   // pkts_per_msg, 1..256
+    uint64_t ppm_hi;                // ceil(2^64 / ppm) (ppm > 1): the quotient is one __umul64hi
+    uint32_t M;                     // msg_numel
+    uint32_t G;                     // items per slot: ceil(M / 1024)
 };
 
 // Record i as the passes see it.
@@ -81,6 +86,12 @@ struct RsRec {
     bool ok;                        // not IGNORED
 };
 
+// POW2: sml_rdma_switch's grid, a shift and a mask.  Otherwise any pkts_per_msg
+// up to 256, with K4's host-computed reciprocal (msg_magic, sml_messages.hip):
+// ppm_hi = ceil(2^64 / ppm) is at most ppm / 2^64 too large as a fraction, idx
+// is below 2^31, so idx * ppm_hi / 2^64 exceeds idx / ppm by less than
+// 2^31 * 256 / 2^64 < 1 / ppm and its floor is the exact quotient.
+template <bool POW2>
 __device__ __forceinline__ RsRec rs_record(const RsArgs& a, uint64_t i) {
     const uint8_t* p = a.arrivals + i * kRsRecordBytes;
     const u4a lo = *reinterpret_cast<const u4a*>(p);           // 8-byte aligned: one dwordx4
@@ -92,8 +103,15 @@ __device__ __forceinline__ RsRec rs_record(const RsArgs& a, uint64_t i) {
     r.addr = ((uint64_t)hi.y << 32) | hi.x;
     const uint32_t idx = lo.y >> 1;
     r.v = lo.y & 1u;
-    r.s = idx >> a.ppm_shift;
-    r.ok = (idx & ((1u << a.ppm_shift) - 1u)) == 0u && r.s < a.S && r.w < a.W && r.src < a.landing_msgs &&
+    bool grid;
+    if constexpr (POW2) {
+        r.s = idx >> a.ppm_shift;
+        grid = (idx & ((1u << a.ppm_shift) - 1u)) == 0u;
+    } else {
+        r.s = a.ppm == 1u ? idx : (uint32_t)__umul64hi((uint64_t)idx, a.ppm_hi);
+        grid = r.s * a.ppm == idx;
+    }
+    r.ok = grid && r.s < a.S && r.w < a.W && r.src < a.landing_msgs &&
            (r.addr & 15u) == 0u && a.fits && r.addr <= a.addr_max;
     return r;
 }
@@ -105,11 +123,12 @@ __device__ __forceinline__ uint32_t rs_count_after(uint32_t c, uint32_t n, uint3
 }
 
 // Pass 1: the (slot, worker) pair's lowest-index record, with its set.
+template <bool POW2>
 __global__ __launch_bounds__(kBlockThreads) void k_rs_claim(RsArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *a.touched_count = 0;      // this call's list starts empty
     const uint64_t stride = (uint64_t)gridDim.x * kBlockThreads;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x; i < a.n; i += stride) {
-        const RsRec r = rs_record(a, i);
+        const RsRec r = rs_record<POW2>(a, i);
         if (r.ok) atomicMax(a.claims + (uint64_t)r.s * kRsMaxWorkers + r.w, ~(((unsigned long long)i << 1) | r.v));
     }
 }
@@ -118,13 +137,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_rs_claim(RsArgs a) {
 // worker u moves its slot's registers once, at its claimed record, so the count
 // record i sees is the call's starting count stepped once per new contributor
 // of its set claimed below i.
+template <bool POW2>
 __global__ __launch_bounds__(kBlockThreads) void k_rs_verdict(RsArgs a) {
     __shared__ uint32_t hist[6];                              // records per verdict, dropped copies
     tally_init(hist);
     const uint32_t all = 0xffffffffu >> (32 - a.W);
     const uint64_t stride = (uint64_t)gridDim.x * kBlockThreads;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x; i < a.n; i += stride) {
-        const RsRec r = rs_record(a, i);
+        const RsRec r = rs_record<POW2>(a, i);
         uint32_t verdict = SML_VERDICT_IGNORED, dropped = 0;
         bool lists = false;
         if (r.ok) {
@@ -329,13 +349,244 @@ __global__ __launch_bounds__(kBlockThreads) void k_rs_apply(RsArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- long messages
+// sml_msg_switch: any msg_numel the sml_msg_* entry points serve, up to 16384
+// words.  Claim and verdict are the passes above; a message no longer fits one
+// wave's registers, so pass 3 becomes two launches, neither with a wave that
+// waits on another:
+//   k_ms_data    wave per (touched slot, item).  A message is ceil(M / 256)
+//                slices of one wave-wide 16-byte access (the last one masked to
+//                its multiple of 16 lanes), a slot is G = ceil(M / 1024) items,
+//                and slice j goes to item j mod G: at most 4 slices a lane at
+//                every M, none idle while another holds 4.  The wave recomputes
+//                its slot's bookkeeping, then does k_rs_apply's sum and results
+//                for its slices alone.  It writes its part of the accumulator
+//                and of the receive regions and nothing else: the registers,
+//                the claim words, the list heads and the links in d_out_imm are
+//                read by the slot's other waves in the same launch.
+//   k_ms_commit  wave per touched slot, after the data pass: the same
+//                bookkeeping, then everything k_rs_apply does to registers —
+//                bitmap, count, exponents, the immediates over the links, the
+//                list head and the claim words cleared.
+constexpr int kMsPer = 4;          // slices per item at most: ceil(M / 256) <= 4 ceil(M / 1024)
+constexpr int kMsInFlight = 2;     // contributors loaded before the first add (k_rs_apply's at 4 chunks a lane)
+
+// A slot's claim words over a wave: lane u < 32 holds worker u's, with its
+// claimed record's exponent bytes and where its message landed.
+struct MsClaims {
+    unsigned long long c;
+    uint64_t iu;
+    uint32_t cs, ed, src;
+    bool live;                      // the claim names a record of this call
+};
+
+__device__ __forceinline__ MsClaims ms_claims(const RsArgs& a, uint32_t s, int lane) {
+    MsClaims k;
+    k.c = lane < (int)kRsMaxWorkers ? a.claims[(uint64_t)s * kRsMaxWorkers + lane] : 0ull;
+    k.iu = (~k.c) >> 1;
+    k.live = k.c != 0ull && k.iu < a.n;
+    k.cs = (uint32_t)((~k.c) & 1ull);
+    k.ed = 0;
+    k.src = 0;
+    if (k.live) {
+        const u2 d = *reinterpret_cast<const u2*>(a.arrivals + k.iu * kRsRecordBytes + 8);
+        k.ed = d.x >> 16;
+        k.src = d.y;
+    }
+    return k;
+}
+
+// One (slot, set) as the call found it — k_fs_apply's bookkeeping: who claims
+// the set, who contributes, who writes over the slot, whose words count.  Read
+// only: both passes get the same answer as long as the commit pass's stores
+// come after it.  False when no claim of the slot concerns the set.
+struct MsSet {
+    uint32_t setmask, clrmask, cmask, wmask, emask;   // ballots over the workers
+    uint32_t bm0, c0, rh;           // bitmap, count, result-list head
+    bool eff;                       // this lane's worker is an effective contributor
+};
+
+__device__ __forceinline__ bool ms_set(const RsArgs& a, uint32_t s, uint32_t v, int lane, const MsClaims& k, MsSet& q) {
+    q.setmask = (uint32_t)__ballot(k.live && k.cs == v);
+    q.clrmask = (uint32_t)__ballot(k.live && k.cs != v);
+    if (!(q.setmask | q.clrmask)) return false;
+    q.bm0 = a.bitmap[2 * s + v];
+    q.c0 = a.count[2 * s + v];
+    const bool contrib = k.live && k.cs == v && !((q.bm0 >> lane) & 1u);
+    q.cmask = (uint32_t)__ballot(contrib);
+    // the bitmap as this lane's claimed record finds it
+    uint32_t before = q.bm0;
+    for (uint32_t x = 0; x < a.W; x++) {
+        const uint64_t ix = shfl_u64(k.iu, (int)x);
+        if (ix < k.iu) {
+            if ((q.setmask >> x) & 1u) before |= 1u << x;
+            if ((q.clrmask >> x) & 1u) before &= ~(1u << x);
+        }
+    }
+    const bool writer = contrib && before == 0u;
+    q.wmask = (uint32_t)__ballot(writer);
+    uint64_t iw = 0;                                   // the last writer's record
+    for (uint32_t m = q.wmask; m; m &= m - 1) {
+        const uint64_t ij = shfl_u64(k.iu, __builtin_ctz(m));
+        iw = ij > iw ? ij : iw;
+    }
+    q.eff = contrib && (q.wmask == 0u || k.iu >= iw);
+    q.emask = (uint32_t)__ballot(q.eff);
+    q.rh = rs_uniform(a.rhead[2 * s + v]);
+    return true;
+}
+
+// Pass 3 of the long path.  Item t = (touched slot t / G, item t % G); the
+// item's slices are g, g + G, g + 2 G, g + 3 G, lane l of slice j holding the
+// 16-byte chunk 64 j + l of the message.
+__global__ __launch_bounds__(kBlockThreads) void k_ms_data(RsArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t all = 0xffffffffu >> (32 - a.W);
+    const uint32_t nwaves = gridDim.x * kWavesPerBlock;
+    const uint32_t nchunks = a.M / 4;                          // 16-byte chunks of a message
+    const uint32_t nitems = *a.touched_count * a.G;
+    for (uint32_t t = blockIdx.x * kWavesPerBlock + wave_index(); t < nitems; t += nwaves) {
+        const uint32_t ts = t / a.G, g = t - ts * a.G;
+        const uint32_t s = rs_uniform(a.touched[ts]);
+        const MsClaims k = ms_claims(a, s, lane);
+        const uint32_t ch0 = g * kWave + (uint32_t)lane, step = a.G * kWave;   // chunk ch0 + i step, i < kMsPer
+#pragma unroll 1
+        for (uint32_t v = 0; v < 2; v++) {
+            MsSet q;
+            if (!ms_set(a, s, v, lane, k, q)) continue;
+            if (!q.cmask && !q.rh) continue;                   // neither a sum nor a result: registers only
+
+            uint8_t* const acc = reinterpret_cast<uint8_t*>(a.acc + ((uint64_t)2 * s + v) * a.M);
+            u4 sum[kMsPer];
+#pragma unroll
+            for (int i = 0; i < kMsPer; i++) {
+                const uint32_t ch = ch0 + i * step;
+                sum[i] = mku4(0u, 0u, 0u, 0u);
+                if (q.wmask == 0u && ch < nchunks) sum[i] = *reinterpret_cast<const u4*>(acc + 16 * ch);
+            }
+            if (q.cmask) {
+                for (uint32_t m = q.emask; m;) {
+                    u4 w[kMsInFlight][kMsPer];
+#pragma unroll
+                    for (int b = 0; b < kMsInFlight; b++) {
+#pragma unroll
+                        for (int i = 0; i < kMsPer; i++) w[b][i] = mku4(0u, 0u, 0u, 0u);
+                        if (m) {
+                            const int j = __builtin_ctz(m);
+                            m &= m - 1;
+                            const uint32_t sj = (uint32_t)__builtin_amdgcn_readlane((int)k.src, j);
+                            const uint8_t* const pl = a.landing + (uint64_t)sj * a.landing_stride;
+#pragma unroll
+                            for (int i = 0; i < kMsPer; i++) {
+                                const uint32_t ch = ch0 + i * step;
+                                if (ch < nchunks)
+                                    w[b][i] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(pl + 16 * ch));
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int b = 0; b < kMsInFlight; b++)
+#pragma unroll
+                        for (int i = 0; i < kMsPer; i++) {
+                            sum[i].x += bswap(w[b][i].x); sum[i].y += bswap(w[b][i].y);
+                            sum[i].z += bswap(w[b][i].z); sum[i].w += bswap(w[b][i].w);
+                        }
+                }
+#pragma unroll
+                for (int i = 0; i < kMsPer; i++) {
+                    const uint32_t ch = ch0 + i * step;
+                    if (ch < nchunks) *reinterpret_cast<u4*>(acc + 16 * ch) = sum[i];
+                }
+            }
+            if (!q.rh) continue;
+
+            // rdma_sender.p4: this item's slices as the wire carries them, to every region a result record names
+            u4 out[kMsPer];
+#pragma unroll
+            for (int i = 0; i < kMsPer; i++)
+                out[i] = mku4(bswap(sum[i].x), bswap(sum[i].y), bswap(sum[i].z), bswap(sum[i].w));
+            for (uint32_t r = q.rh; r;) {
+                const uint64_t i = r - 1u;
+                const uint8_t* const rec = a.arrivals + i * kRsRecordBytes;
+                const uint32_t w = rs_uniform(*reinterpret_cast<const uint32_t*>(rec));
+                const uint64_t addr = uniform_u64(*reinterpret_cast<const unsigned long long*>(rec + 16));
+                const uint32_t dm = a.drop ? a.drop[i] : 0u;
+                const uint32_t to = a.verdict[i] == SML_VERDICT_BROADCAST ? all : 1u << w;
+                r = rs_uniform(a.out_imm[i]);                  // the link: the commit pass puts the immediate there
+                for (uint32_t m = rs_uniform(to & ~dm); m; m &= m - 1) {
+                    uint8_t* const dst = a.rx + (uint64_t)__builtin_ctz(m) * a.rx_bytes + addr;
+#pragma unroll
+                    for (int x = 0; x < kMsPer; x++) {
+                        const uint32_t ch = ch0 + x * step;
+                        if (ch < nchunks) SML_NT_STORE16(out[x], dst + 16 * ch);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Pass 4 of the long path, wave per touched slot: the registers.
+__global__ __launch_bounds__(kBlockThreads) void k_ms_commit(RsArgs a) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t nwaves = gridDim.x * kWavesPerBlock;
+    const uint32_t ntouched = *a.touched_count;
+    for (uint32_t t = blockIdx.x * kWavesPerBlock + wave_index(); t < ntouched; t += nwaves) {
+        const uint32_t s = rs_uniform(a.touched[t]);
+        const MsClaims k = ms_claims(a, s, lane);
+#pragma unroll 1
+        for (uint32_t v = 0; v < 2; v++) {
+            MsSet q;
+            if (!ms_set(a, s, v, lane, k, q)) continue;
+            if (lane == 0) {
+                a.bitmap[2 * s + v] = (q.bm0 | q.setmask) & ~q.clrmask;
+                a.count[2 * s + v] = rs_count_after(q.c0, (uint32_t)__builtin_popcount(q.cmask), a.W);
+            }
+            if (!q.cmask && !q.rh) continue;
+            uint32_t ex = a.exps[2 * s + v];
+            if (q.cmask) {
+                // exponents: signed int8 max, each byte on its own; -128 is the identity
+                int e0 = q.eff ? (int)(int8_t)(k.ed & 0xffu) : -128;
+                int e1 = q.eff ? (int)(int8_t)((k.ed >> 8) & 0xffu) : -128;
+#pragma unroll
+                for (int d = 1; d < (int)kRsMaxWorkers; d <<= 1) {
+                    const int o0 = __shfl_xor(e0, d), o1 = __shfl_xor(e1, d);
+                    e0 = o0 > e0 ? o0 : e0;
+                    e1 = o1 > e1 ? o1 : e1;
+                }
+                e0 = (int)rs_uniform((uint32_t)e0);            // lane 0: the max over lanes 0..31
+                e1 = (int)rs_uniform((uint32_t)e1);
+                if (q.wmask == 0u) {
+                    e0 = rs_max_i8(ex & 0xffu, (uint32_t)e0 & 0xffu);
+                    e1 = rs_max_i8((ex >> 8) & 0xffu, (uint32_t)e1 & 0xffu);
+                }
+                ex = ((uint32_t)e0 & 0xffu) | (((uint32_t)e1 & 0xffu) << 8);
+                if (lane == 0) a.exps[2 * s + v] = ex;
+            }
+            if (!q.rh) continue;
+            for (uint32_t r = q.rh; r;) {
+                const uint64_t i = r - 1u;
+                const uint32_t imm = rs_uniform(*reinterpret_cast<const uint32_t*>(a.arrivals + i * kRsRecordBytes + 8));
+                r = rs_uniform(a.out_imm[i]);                  // the link, before the immediate takes its place
+                if (lane == 0) a.out_imm[i] = (imm & 0xffffu) | (ex << 16);
+            }
+            if (lane == 0) a.rhead[2 * s + v] = 0u;            // the next call's lists start empty
+        }
+        // the next call's claims start empty
+        if (lane < (int)kRsMaxWorkers && k.c != 0ull) a.claims[(uint64_t)s * kRsMaxWorkers + lane] = 0ull;
+    }
+}
+
 // The pieces of d_state.
 struct RsLayout {
     uint64_t claims, bitmap, count, exps, rhead, touched, acc, total;
 };
 
-static bool rs_layout(uint32_t S, uint32_t M, RsLayout& l) {
-    if (!valid_packet(M) || S == 0 || S > kRsMaxSlots) return false;
+
+// sml_rdma_switch's pool holds packet-sized messages, sml_msg_switch's (any_msg)
+// every length the sml_msg_* entry points serve: the same layout, M general.
+static bool rs_layout(uint32_t S, uint32_t M, bool any_msg, RsLayout& l) {
+    if (!(any_msg ? sml_msg_numel_supported(M) != 0 : valid_packet(M)) || S == 0 || S > kRsMaxSlots) return false;
     l.claims = kRsHead;
     l.bitmap = l.claims + 8ull * kRsMaxWorkers * S;
     l.count = l.bitmap + 8ull * S;
@@ -347,36 +598,28 @@ static bool rs_layout(uint32_t S, uint32_t M, RsLayout& l) {
     return true;
 }
 
-}  // namespace sml
-
-using namespace sml;
-
-extern "C" {
-
-uint64_t sml_rdma_switch_state_bytes(uint32_t num_slots, uint32_t msg_numel) {
-    RsLayout l;
-    return rs_layout(num_slots, msg_numel, l) ? l.total : 0;
-}
-
-sml_status_t sml_rdma_switch_reset(void* d_state, uint32_t num_slots, uint32_t msg_numel, void* stream) {
+static sml_status_t rs_reset(void* d_state, uint32_t S, uint32_t M, bool any_msg, void* stream) {
     if (!d_state) return SML_ERR_INVALID_ARG;
     RsLayout l;
-    if (!rs_layout(num_slots, msg_numel, l)) return SML_ERR_UNSUPPORTED;
+    if (!rs_layout(S, M, any_msg, l)) return SML_ERR_UNSUPPORTED;
     if (!aligned16(d_state)) return SML_ERR_ALIGNMENT;
     // everything but the accumulators: a slot's words are written before they are read
     return hip_check(hipMemsetAsync(d_state, 0, l.acc, (hipStream_t)stream));
 }
 
-sml_status_t sml_rdma_switch(const sml_rdma_switch_params* prm, const sml_rdma_arrival* d_arrivals, uint64_t n,
-                             const void* landing, uint64_t landing_stride, uint64_t landing_msgs, void* d_state,
-                             void* rx, uint64_t rx_bytes, const uint32_t* d_drop, uint32_t* d_out_imm,
-                             uint8_t* d_verdict, uint64_t* d_counts, void* stream) {
+// Both families' call: every check before any launch, in one order, then the
+// record passes and the family's own data movement.
+static sml_status_t rs_call(bool any_msg, const sml_rdma_switch_params* prm, const sml_rdma_arrival* d_arrivals,
+                            uint64_t n, const void* landing, uint64_t landing_stride, uint64_t landing_msgs,
+                            void* d_state, void* rx, uint64_t rx_bytes, const uint32_t* d_drop, uint32_t* d_out_imm,
+                            uint8_t* d_verdict, uint64_t* d_counts, void* stream) {
     if (!prm) return SML_ERR_INVALID_ARG;
     if (n && (!d_arrivals || !landing || !d_state || !rx || !d_out_imm || !d_verdict)) return SML_ERR_INVALID_ARG;
     const uint32_t M = prm->msg_numel, S = prm->num_slots, W = prm->num_workers, ppm = prm->pkts_per_msg;
     RsLayout l;
-    if (!rs_layout(S, M, l) || W == 0 || W > kRsMaxWorkers || n > kRsMaxRecords) return SML_ERR_UNSUPPORTED;
-    if (ppm != 1 && ppm != 2 && ppm != 4 && ppm != 8 && ppm != 16) return SML_ERR_UNSUPPORTED;
+    if (!rs_layout(S, M, any_msg, l) || W == 0 || W > kRsMaxWorkers || n > kRsMaxRecords) return SML_ERR_UNSUPPORTED;
+    if (any_msg ? ppm == 0 || ppm > 256 : ppm != 1 && ppm != 2 && ppm != 4 && ppm != 8 && ppm != 16)
+        return SML_ERR_UNSUPPORTED;
     if (n == 0) return SML_OK;
     if (!aligned16(landing) || landing_stride % 16 || landing_stride < 4ull * M) return SML_ERR_ALIGNMENT;
     if (!aligned16(rx) || rx_bytes % 16 || !aligned16(d_state)) return SML_ERR_ALIGNMENT;
@@ -409,16 +652,69 @@ sml_status_t sml_rdma_switch(const sml_rdma_switch_params* prm, const sml_rdma_a
     a.acc = reinterpret_cast<uint32_t*>(st8 + l.acc);
     a.S = S;
     a.W = W;
-    a.ppm_shift = (uint32_t)__builtin_ctz(ppm);
 
     hipStream_t st = (hipStream_t)stream;
     const uint32_t grecords = grid_for_vec(n);
-    k_rs_claim<<<grecords, kBlockThreads, 0, st>>>(a);
-    k_rs_verdict<<<grecords, kBlockThreads, 0, st>>>(a);
     // at most one touched slot per record, and per slot of the pool
-    const uint32_t gslots = grid_for_tiles(n < S ? n : S);
-    dispatch_packet(M, [&](auto Mc) { k_rs_apply<Mc()><<<gslots, kBlockThreads, 0, st>>>(a); });
+    const uint64_t nslots = n < S ? n : S;
+    if (!any_msg) {
+        a.ppm_shift = (uint32_t)__builtin_ctz(ppm);
+        k_rs_claim<true><<<grecords, kBlockThreads, 0, st>>>(a);
+        k_rs_verdict<true><<<grecords, kBlockThreads, 0, st>>>(a);
+        const uint32_t gslots = grid_for_tiles(nslots);
+        dispatch_packet(M, [&](auto Mc) { k_rs_apply<Mc()><<<gslots, kBlockThreads, 0, st>>>(a); });
+        return launch_check();
+    }
+    a.ppm = ppm;
+    a.ppm_hi = ppm == 1 ? 0 : ~0ull / ppm + 1;     // a power of two: 2^64 / ppm, else floor + 1 = ceil
+    a.M = M;
+    a.G = (M + 1023) / 1024;
+    k_rs_claim<false><<<grecords, kBlockThreads, 0, st>>>(a);
+    k_rs_verdict<false><<<grecords, kBlockThreads, 0, st>>>(a);
+    // the touched count is known on the device only: a wave per item of every slot that can be touched
+    k_ms_data<<<grid_for_tiles(nslots * a.G), kBlockThreads, 0, st>>>(a);
+    k_ms_commit<<<grid_for_tiles(nslots), kBlockThreads, 0, st>>>(a);
     return launch_check();
+}
+
+}  // namespace sml
+
+using namespace sml;
+
+extern "C" {
+
+uint64_t sml_rdma_switch_state_bytes(uint32_t num_slots, uint32_t msg_numel) {
+    RsLayout l;
+    return rs_layout(num_slots, msg_numel, false, l) ? l.total : 0;
+}
+
+sml_status_t sml_rdma_switch_reset(void* d_state, uint32_t num_slots, uint32_t msg_numel, void* stream) {
+    return rs_reset(d_state, num_slots, msg_numel, false, stream);
+}
+
+sml_status_t sml_rdma_switch(const sml_rdma_switch_params* prm, const sml_rdma_arrival* d_arrivals, uint64_t n,
+                             const void* landing, uint64_t landing_stride, uint64_t landing_msgs, void* d_state,
+                             void* rx, uint64_t rx_bytes, const uint32_t* d_drop, uint32_t* d_out_imm,
+                             uint8_t* d_verdict, uint64_t* d_counts, void* stream) {
+    return rs_call(false, prm, d_arrivals, n, landing, landing_stride, landing_msgs, d_state, rx, rx_bytes, d_drop,
+                   d_out_imm, d_verdict, d_counts, stream);
+}
+
+uint64_t sml_msg_switch_state_bytes(uint32_t num_slots, uint32_t msg_numel) {
+    RsLayout l;
+    return rs_layout(num_slots, msg_numel, true, l) ? l.total : 0;
+}
+
+sml_status_t sml_msg_switch_reset(void* d_state, uint32_t num_slots, uint32_t msg_numel, void* stream) {
+    return rs_reset(d_state, num_slots, msg_numel, true, stream);
+}
+
+sml_status_t sml_msg_switch(const sml_rdma_switch_params* prm, const sml_rdma_arrival* d_arrivals, uint64_t n,
+                            const void* landing, uint64_t landing_stride, uint64_t landing_msgs, void* d_state,
+                            void* rx, uint64_t rx_bytes, const uint32_t* d_drop, uint32_t* d_out_imm,
+                            uint8_t* d_verdict, uint64_t* d_counts, void* stream) {
+    return rs_call(true, prm, d_arrivals, n, landing, landing_stride, landing_msgs, d_state, rx, rx_bytes, d_drop,
+                   d_out_imm, d_verdict, d_counts, stream);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@ RDMA_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_switch.h")   # i
 RDMA_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_worker.h")   # included by switchml_hip.h
 FRAME_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_frame_worker.h")  # included by switchml_hip.h
 MESSAGES_HEADER_PATH = os.path.join(_INCLUDE, "switchml_messages.h")          # included by switchml_hip.h
+MSG_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_msg_switch.h")      # included by switchml_hip.h
 
 # sml_status_t
 SML_OK, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_ERR_ALIGNMENT, SML_ERR_HIP = range(5)
@@ -249,6 +250,14 @@ MESSAGES_SIGNATURES = {
     "sml_msg_roundtrip_loopback": (i32, [vp, vp, i32, u64, u32, u16, vp, vp, u32, vp]),
 }
 
+# include/switchml_msg_switch.h, likewise (tests/test_msg_switch_cpu.py): the RDMA switch's three calls
+# for messages of any supported length
+MSG_SWITCH_SIGNATURES = {
+    "sml_msg_switch_state_bytes": RDMA_SWITCH_SIGNATURES["sml_rdma_switch_state_bytes"],
+    "sml_msg_switch_reset": RDMA_SWITCH_SIGNATURES["sml_rdma_switch_reset"],
+    "sml_msg_switch": RDMA_SWITCH_SIGNATURES["sml_rdma_switch"],
+}
+
 _lib = None
 
 
@@ -262,7 +271,8 @@ def lib():
                           "(or __graft_entry__.build()); there is no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES, **RDMA_WORKER_SIGNATURES,
-                                      **FRAME_WORKER_SIGNATURES, **MESSAGES_SIGNATURES}.items():
+                                      **FRAME_WORKER_SIGNATURES, **MESSAGES_SIGNATURES,
+                                      **MSG_SWITCH_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

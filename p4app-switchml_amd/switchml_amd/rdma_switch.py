@@ -1,11 +1,12 @@
-"""The switch between RDMA workers (sml_rdma_switch, DESIGN §9 F4 "Switch
-side"): the slot pool that aggregates a batch of landed messages per call and
-writes the results into the workers' receive regions."""
+"""The switch between RDMA workers (sml_rdma_switch and, for long messages,
+sml_msg_switch: DESIGN §9 F4 "Switch side"): the slot pool that aggregates a
+batch of landed messages per call and writes the results into the workers'
+receive regions."""
 from __future__ import annotations
 
 import ctypes
 
-from .abi import SML_ERR_UNSUPPORTED, RdmaArrival, RdmaSwitchParams, SwitchMLError, call, lib
+from .abi import PACKET_NUMELS, SML_ERR_UNSUPPORTED, RdmaArrival, RdmaSwitchParams, SwitchMLError, call, lib
 from .glue import _dev, _opt, _stream, _torch
 
 ARRIVAL_BYTES = ctypes.sizeof(RdmaArrival)
@@ -20,7 +21,10 @@ def rdma_rkey(slot: int, set_: int, pkts_per_msg: int) -> int:
 
 class RdmaSwitch:
     """Owns the message slots' registers on the device; `step` is one call
-    over a batch of completion records."""
+    over a batch of completion records.  A packet-sized message with
+    pkts_per_msg 1, 2, 4, 8 or 16 runs on sml_rdma_switch*; every other
+    supported length (a multiple of 64 up to 16384 words) and pkts_per_msg up
+    to 256 on sml_msg_switch*, chosen here once."""
 
     def __init__(self, num_workers: int, num_slots: int, msg_numel: int = 1024, pkts_per_msg: int = 4,
                  device="cuda"):
@@ -28,18 +32,21 @@ class RdmaSwitch:
         self.params = RdmaSwitchParams(num_workers, num_slots, msg_numel, pkts_per_msg)
         self.num_workers, self.num_slots = num_workers, num_slots
         self.msg_numel, self.pkts_per_msg = msg_numel, pkts_per_msg
-        nbytes = int(lib().sml_rdma_switch_state_bytes(num_slots, msg_numel))
+        # the family of entry points this object calls: "sml_rdma_switch" or "sml_msg_switch"
+        short = msg_numel in PACKET_NUMELS and pkts_per_msg in (1, 2, 4, 8, 16)
+        self.entry = "sml_rdma_switch" if short else "sml_msg_switch"
+        nbytes = int(getattr(lib(), self.entry + "_state_bytes")(num_slots, msg_numel))
         if nbytes == 0:
-            raise SwitchMLError("sml_rdma_switch_state_bytes", SML_ERR_UNSUPPORTED)
+            raise SwitchMLError(self.entry + "_state_bytes", SML_ERR_UNSUPPORTED)
         self.state = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
         # CONSUMED, BROADCAST, RETRANSMIT, IGNORED, DEFERRED, dropped copies: running
         self.counts = torch.zeros(6, dtype=torch.int64, device=device)
         self.reset()
 
     def reset(self, stream=None):
-        """Every slot empty, both sets (sml_rdma_switch_reset); the counters go to zero."""
+        """Every slot empty, both sets (the family's _reset); the counters go to zero."""
         torch = _torch()
-        call("sml_rdma_switch_reset", _dev(self.state, torch.int64, "state"), self.num_slots, self.msg_numel,
+        call(self.entry + "_reset", _dev(self.state, torch.int64, "state"), self.num_slots, self.msg_numel,
              _stream(stream, self.state))
         self.counts.zero_()
 
@@ -78,7 +85,7 @@ class RdmaSwitch:
             out_imm = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         if verdict.numel() < n or out_imm.numel() < n or (drop is not None and drop.numel() < n):
             raise ValueError("verdict, out_imm and drop hold an entry per record")
-        call("sml_rdma_switch", ctypes.byref(self.params), _dev(records, records.dtype, "arrivals"), n,
+        call(self.entry, ctypes.byref(self.params), _dev(records, records.dtype, "arrivals"), n,
              _dev(landing, landing.dtype, "landing"), landing.shape[1] * landing.element_size(), landing.shape[0],
              _dev(self.state, torch.int64, "state"), _dev(rx, rx.dtype, "rx"), rx.shape[1] * rx.element_size(),
              _opt(drop, torch.int32, "drop"), _dev(out_imm, torch.int32, "out_imm"),

@@ -23,13 +23,15 @@ and behind the switch call, beside sml_stream_copy of its own algorithmic bytes
 (main_deliver below); --deliver-trace: a few untimed calls of those arms, to
 run under rocprofv3 --kernel-trace.
 --rdma: the RDMA switch (sml_rdma_switch) on the same two shapes, beside the
-copy and the frame path (main_rdma below).
+copy and the frame path (main_rdma below); --rdma --msg-numel M[,M...]: the
+RDMA switch at those message lengths, sml_msg_switch beside sml_rdma_switch
+where both serve one and beside the copy (main_rdma_long below).
 --rdma-worker: the RDMA worker's completion loop (sml_rdma_worker_poll) beside
 the per-packet exchange bursts and the copy (main_rdma_worker below).
 --frame-worker: the DPDK worker's receive loop (sml_frame_worker_poll) beside
 the bulk tx + rx pair over as many frames and the copy (main_frame_worker below).
 Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace | --rdma [OUT.json]
-       | --rdma-worker [OUT.json] | --frame-worker [OUT.json]"""
+       | --rdma --msg-numel M[,M...] [OUT.json] | --rdma-worker [OUT.json] | --frame-worker [OUT.json]"""
 import json
 import os
 import statistics
@@ -370,6 +372,96 @@ def main_rdma(out_path=None, rounds=7, W=8, M=256):
     return 0
 
 
+def main_rdma_long(out_path, Ms, rounds=7, W=8):
+    """The RDMA switch at the message lengths `Ms`, on main_rdma's method: a
+    256-slot window, and a batch of 16384 * 1024 / M slots (the same bytes at
+    every M), a message per (slot, worker), every call completing its slots and
+    writing W results per slot.  M = 1024 runs both families on records that
+    differ in pkts_per_msg alone (4: sml_rdma_switch, 3: sml_msg_switch); any
+    other M the long path, beside sml_stream_copy of the call's algorithmic
+    bytes (every message and record read once, the accumulators written once, W
+    results per slot)."""
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream()
+    arms, meta = {}, {}
+    for M in Ms:
+        paths = {"sml_rdma_switch": 4, "sml_msg_switch": 3} if M == 1024 else {"sml_msg_switch": M // 256}
+        for shape, (S, nbuf, reps) in {"window": (256, 2, 200), "batch": (16384 * 1024 // M, 4, 10)}.items():
+            F, tag = S * W, f"m{M}_{shape}"
+            landing = [torch.empty((F, 4 * M), dtype=torch.uint8, device=dev).random_(0, 256) for _ in range(nbuf)]
+            rx = torch.zeros((W, S * 4 * M), dtype=torch.uint8, device=dev)
+            vd = torch.empty(F, dtype=torch.uint8, device=dev)
+            imm = torch.zeros(F, dtype=torch.int32, device=dev)
+            alg = F * 4 * M + 24 * F + S * 4 * M + W * S * 4 * M
+            for entry, ppm in paths.items():
+                rs = sw.RdmaSwitch(W, S, M, ppm, device=dev)
+                assert rs.entry == entry
+                recs = []
+                for k in range(nbuf):                        # message slot * W + w, in a seeded arrival order
+                    order = np.random.default_rng(80 + k).permutation(F)
+                    a = np.zeros(F, dtype=np.dtype(sw.rdma_switch.ARRIVAL_FIELDS))
+                    a["worker"], a["rkey"], a["imm"] = order % W, (order // W * ppm) << 1 | (k & 1), order // W
+                    a["src"], a["addr"] = order, (order // W) * 4 * M
+                    recs.append(torch.from_numpy(a.view(np.uint8)).to(dev))
+                # checked before anything is timed: every slot completes, the regions hold slot 0's wrapping sum
+                rs.step(recs[0], landing[0], rx, verdict=vd, out_imm=imm)
+                torch.cuda.synchronize()
+                assert rs.counts.tolist() == [S * (W - 1), S, 0, 0, 0, 0], rs.counts.tolist()
+                want = landing[0][:W].cpu().numpy().view(">u4").astype(np.uint32).sum(axis=0, dtype=np.uint32)
+                for u in (0, W - 1):
+                    assert np.array_equal(rx[u, :4 * M].cpu().numpy().view(">u4").astype(np.uint32), want)
+                rs.reset()
+
+                def call(k, rs=rs, recs=recs, landing=landing, rx=rx, vd=vd, imm=imm, nbuf=nbuf):
+                    rs.step(recs[k % nbuf], landing[k % nbuf], rx, verdict=vd, out_imm=imm, stream=st)
+
+                arms[f"{tag}_{entry}"] = (call, reps)
+            half = (alg // 2 + 4095) // 4096 * 4096
+            src = [torch.empty(half, dtype=torch.uint8, device=dev).random_(0, 256) for _ in range(nbuf)]
+            dst = [torch.empty(half, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+
+            def copy(k, src=src, dst=dst, nbuf=nbuf):
+                sw.stream_copy(src[k % nbuf], dst[k % nbuf], stream=st)
+
+            arms[tag + "_stream_copy"] = (copy, reps)
+            meta[tag] = dict(msg_numel=M, num_slots=S, messages_per_call=F, results_written=W * S, algorithmic_bytes=alg,
+                             copy_bytes_moved=2 * half, entries=list(paths))
+    times = {name: [] for name in arms}
+    step = [0]
+    for _ in range(rounds):
+        for name, (fn, reps) in arms.items():
+            assert step[0] % 2 == 0 and reps % 2 == 0            # a switch's calls alternate its slots' sets
+            times[name].append(timed(fn, st, reps, step))
+    med = {name: statistics.median(v) for name, v in times.items()}
+    res = {name: {"median_us": round(med[name], 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+           for name, v in times.items()}
+    for tag, m in meta.items():
+        shape = tag.split("_")[1]
+        old = f"m1024_{shape}_sml_rdma_switch"                     # time per byte against the existing kernel's
+        for entry in m.pop("entries"):
+            us = med[f"{tag}_{entry}"]
+            res[f"{tag}_{entry}"].update(m, TBps_algorithmic=round(m["algorithmic_bytes"] / us / 1e6, 3),
+                                         time_over_stream_copy=round(us / med[tag + "_stream_copy"], 3))
+            if old in med:
+                res[f"{tag}_{entry}"]["time_per_byte_over_m1024_sml_rdma_switch"] = round(
+                    us / m["algorithmic_bytes"] / (med[old] / meta[f"m1024_{shape}"]["algorithmic_bytes"]), 3)
+        res[tag + "_stream_copy"].update(TBps=round(m["copy_bytes_moved"] / med[tag + "_stream_copy"] / 1e6, 3))
+    text = json.dumps({
+        "what": f"side measurement (not bench.py's headline): the RDMA switch at msg_numel {Ms}, W={W}; window: 256 "
+                f"slots; batch: 16384 * 1024 / msg_numel slots; a message per (slot, worker), every call completes "
+                f"its slots and writes W results per slot; msg_numel 1024: sml_rdma_switch (pkts_per_msg 4) and "
+                f"sml_msg_switch (pkts_per_msg 3) on the same messages, else sml_msg_switch (pkts_per_msg = "
+                f"msg_numel / 256); beside sml_stream_copy of the call's algorithmic bytes; all arms in one process, "
+                f"{rounds} interleaved rounds, every timing warmed, medians with the rounds' min-max, HIP events; "
+                f"nothing here was measured before this file was written",
+        "device": torch.cuda.get_device_name(0), "arms": res}, indent=1)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main_rdma_worker(out_path=None, rounds=7, W=8, M=1024, reps=10):
     """The RDMA worker's completion loop (sml_rdma_worker_poll: judge, accept)
     at Q = 16384 and Q = 64 queue pairs: FLOAT32, a slice of 4 Q M elements, a
@@ -589,6 +681,8 @@ if __name__ == "__main__":
         sys.exit(main_frame_worker(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--rdma-worker":
         sys.exit(main_rdma_worker(sys.argv[2] if len(sys.argv) > 2 else None))
+    if len(sys.argv) > 3 and sys.argv[1] == "--rdma" and sys.argv[2] == "--msg-numel":
+        sys.exit(main_rdma_long(sys.argv[4] if len(sys.argv) > 4 else None, [int(m) for m in sys.argv[3].split(",")]))
     if len(sys.argv) > 1 and sys.argv[1] == "--rdma":
         sys.exit(main_rdma(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 1 and sys.argv[1] == "--deliver":
