@@ -46,6 +46,9 @@
  *   the switch such workers talk to: sml_msg_switch (switchml_msg_switch.h),
  *     sml_rdma_switch's slot pool, worker bitmap, retransmission and receive
  *     regions for every msg_numel served here and pkts_per_msg up to 256;
+ *   the completion loop that drives it message by message: sml_msg_worker_begin
+ *     / _poll / _resend (switchml_msg_worker.h), sml_rdma_worker's per-QP state
+ *     and records at the same msg_numel and pkts_per_msg;
  *   a W-worker switch step on whole planes, without a slot pool:
  *     sml_msg_exponents per worker -> sml_switch_exps ->
  *     sml_msg_quantize_pack with the global exponents per worker ->
@@ -54,8 +57,8 @@
  *     sml_msg_dequantize.
  * Not served at msg_numel > 1024 (they keep returning SML_ERR_UNSUPPORTED): the
  * per-packet bursts, the batched round trip, the DPDK frames, sml_rdma_switch
- * itself (its sml_msg_switch twin serves them), the sml_rdma_worker_* calls and
- * the client's config keys. */
+ * and the sml_rdma_worker_* calls themselves (their sml_msg_switch and
+ * sml_msg_worker_* twins serve them) and the client's config keys. */
 #ifndef SWITCHML_MESSAGES_H_
 #define SWITCHML_MESSAGES_H_
 

@@ -38,12 +38,10 @@
 // two multiplications with host-computed reciprocals (msg_magic), exact for
 // every numel < 2^56: no division in the kernel.
 #include "sml_host.h"
+#include "sml_msg_deal.h"
 #include "switchml_messages.h"
 
 namespace sml {
-
-constexpr int kMsgU = 4;                       // slices a wave keeps of its message
-constexpr int kMsgMaxWaves = 16;               // waves of the largest message = of the largest workgroup
 
 template <class T>
 struct MsgArgs {
@@ -67,12 +65,6 @@ struct MsgArgs {
 __device__ __forceinline__ void msg_build_lut(float* lut, uint32_t W) {
     for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) lut[i] = scale_for(W, (int)(int8_t)(uint8_t)i);
     __syncthreads();
-}
-
-// Offset inside its message of the vector this lane holds as slice u of wave
-// `part` of the message.
-__device__ __forceinline__ uint32_t msg_offset(uint32_t wpm, int u, uint32_t part, int lane) {
-    return ((uint32_t)u * wpm + part) * 256u + (uint32_t)lane * 4u;
 }
 
 // The loads of this wave's slices of message `msg`: whole vectors inside the

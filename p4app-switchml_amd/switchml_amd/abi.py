@@ -23,6 +23,7 @@ RDMA_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_rdma_worker.h")   # i
 FRAME_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_frame_worker.h")  # included by switchml_hip.h
 MESSAGES_HEADER_PATH = os.path.join(_INCLUDE, "switchml_messages.h")          # included by switchml_hip.h
 MSG_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_msg_switch.h")      # included by switchml_hip.h
+MSG_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_msg_worker.h")      # included by switchml_hip.h
 
 # sml_status_t
 SML_OK, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_ERR_ALIGNMENT, SML_ERR_HIP = range(5)
@@ -258,6 +259,11 @@ MSG_SWITCH_SIGNATURES = {
     "sml_msg_switch": RDMA_SWITCH_SIGNATURES["sml_rdma_switch"],
 }
 
+# include/switchml_msg_worker.h, likewise (tests/test_msg_worker_cpu.py): the RDMA worker's five calls
+# for messages of any supported length
+MSG_WORKER_SIGNATURES = {name.replace("sml_rdma_worker", "sml_msg_worker"): sig
+                         for name, sig in RDMA_WORKER_SIGNATURES.items()}
+
 _lib = None
 
 
@@ -272,7 +278,7 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES, **RDMA_WORKER_SIGNATURES,
                                       **FRAME_WORKER_SIGNATURES, **MESSAGES_SIGNATURES,
-                                      **MSG_SWITCH_SIGNATURES}.items():
+                                      **MSG_SWITCH_SIGNATURES, **MSG_WORKER_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -1,5 +1,5 @@
-"""One RDMA worker thread's completion loop on the device (sml_rdma_worker_*,
-DESIGN §9 F4 "Worker side"): the per-QP state (expected message id, kept
+"""One RDMA worker thread's completion loop on the device (sml_rdma_worker_*
+and, for long messages, sml_msg_worker_*: DESIGN §9 F4 "Worker side"): the per-QP state (expected message id, kept
 exponent, pool flag) lives in device memory; `begin` posts a slice's first
 batch, `poll` accepts a batch of completions and builds each QP's next
 message, `resend` repeats an outstanding one.  What they return are
@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 
-from .abi import (BFLOAT16, FLOAT16, FLOAT32, INT32, SML_ERR_UNSUPPORTED, RdmaCompletion, RdmaWorkerParams,
+from .abi import (BFLOAT16, FLOAT16, FLOAT32, INT32, PACKET_NUMELS, SML_ERR_UNSUPPORTED, RdmaCompletion, RdmaWorkerParams,
                   SwitchMLError, call, lib)
 from .glue import _dev, _stream, _torch
 from .rdma_switch import ARRIVAL_BYTES
@@ -19,7 +19,11 @@ COMPLETION_FIELDS = [("qpn", "<u4"), ("imm", "<u4")]
 
 
 class RdmaWorker:
-    """Owns one worker thread's QP state and verdict counts on the device."""
+    """Owns one worker thread's QP state and verdict counts on the device.  A
+    packet-sized message with pkts_per_msg 1, 2, 4, 8 or 16 runs on
+    sml_rdma_worker_*; every other supported length (a multiple of 64 up to
+    16384 words) and pkts_per_msg up to 256 on sml_msg_worker_*, chosen here
+    once."""
 
     def __init__(self, worker: int, num_workers: int, num_qps: int, msg_numel: int = 1024, pkts_per_msg: int = 4,
                  first_slot: int = 0, src_base: int = 0, dtype=None, device="cuda", flags: int = 0):
@@ -31,9 +35,12 @@ class RdmaWorker:
         self.dtype, self.num_qps, self.msg_numel = dtype, num_qps, msg_numel
         self.params = RdmaWorkerParams(worker, num_workers, code, msg_numel, pkts_per_msg, num_qps, first_slot,
                                        src_base, flags)
-        nbytes = int(lib().sml_rdma_worker_state_bytes(num_qps))
+        # the family of entry points this object calls: "sml_rdma_worker" or "sml_msg_worker"
+        short = msg_numel in PACKET_NUMELS and pkts_per_msg in (1, 2, 4, 8, 16)
+        self.entry = "sml_rdma_worker" if short else "sml_msg_worker"
+        nbytes = int(getattr(lib(), self.entry + "_state_bytes")(num_qps))
         if nbytes == 0:
-            raise SwitchMLError("sml_rdma_worker_state_bytes", SML_ERR_UNSUPPORTED)
+            raise SwitchMLError(self.entry + "_state_bytes", SML_ERR_UNSUPPORTED)
         self.state = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
         # WRONG, POSTED, FINISHED, IGNORED: running
         self.counts = torch.zeros(4, dtype=torch.int64, device=device)
@@ -54,7 +61,7 @@ class RdmaWorker:
 
     def reset(self, stream=None):
         """No slice under way, every QP's pool flag 1; the counters go to zero."""
-        call("sml_rdma_worker_reset", self._state(), self.num_qps, _stream(stream, self.state))
+        call(self.entry + "_reset", self._state(), self.num_qps, _stream(stream, self.state))
         self.counts.zero_()
 
     def begin(self, x, out, tx, stream=None):
@@ -64,7 +71,7 @@ class RdmaWorker:
         if x.numel() != out.numel():
             raise ValueError("x and out must hold the same number of elements")
         sends = self._sends(self.num_qps)
-        call("sml_rdma_worker_begin", ctypes.byref(self.params), _dev(x, self.dtype, "x"),
+        call(self.entry + "_begin", ctypes.byref(self.params), _dev(x, self.dtype, "x"),
              _dev(out, self.dtype, "out"), x.numel(), self._state(), self._buffer(tx, "tx"),
              _dev(sends, sends.dtype, "sends"), _stream(stream, self.state))
         return sends
@@ -90,7 +97,7 @@ class RdmaWorker:
         n = nbytes // COMPLETION_BYTES
         sends = self._sends(n)
         verdict = torch.empty(max(1, n), dtype=torch.uint8, device=dev)
-        call("sml_rdma_worker_poll", ctypes.byref(self.params), _dev(completions, completions.dtype, "completions"), n,
+        call(self.entry + "_poll", ctypes.byref(self.params), _dev(completions, completions.dtype, "completions"), n,
              self._state(), self._buffer(rx, "rx"), self._buffer(tx, "tx"), _dev(sends, sends.dtype, "sends"),
              _dev(verdict, torch.uint8, "verdict"), _dev(self.counts, torch.int64, "counts"),
              _stream(stream, self.state))
@@ -104,6 +111,6 @@ class RdmaWorker:
             qpns = torch.tensor(list(qpns), dtype=torch.int32).to(self.state.device)
         n = qpns.numel()
         sends = self._sends(n)
-        call("sml_rdma_worker_resend", ctypes.byref(self.params), _dev(qpns, torch.int32, "qpns"), n, self._state(),
+        call(self.entry + "_resend", ctypes.byref(self.params), _dev(qpns, torch.int32, "qpns"), n, self._state(),
              _dev(sends, sends.dtype, "sends"), _stream(stream, self.state))
         return sends[:n]

@@ -27,11 +27,15 @@ copy and the frame path (main_rdma below); --rdma --msg-numel M[,M...]: the
 RDMA switch at those message lengths, sml_msg_switch beside sml_rdma_switch
 where both serve one and beside the copy (main_rdma_long below).
 --rdma-worker: the RDMA worker's completion loop (sml_rdma_worker_poll) beside
-the per-packet exchange bursts and the copy (main_rdma_worker below).
+the per-packet exchange bursts and the copy (main_rdma_worker below);
+--rdma-worker --msg-numel M[,M...]: the loop at those message lengths,
+sml_msg_worker_poll beside the copy and, at 1024, beside sml_rdma_worker_poll
+(main_msg_worker below).
 --frame-worker: the DPDK worker's receive loop (sml_frame_worker_poll) beside
 the bulk tx + rx pair over as many frames and the copy (main_frame_worker below).
 Usage: bench_switch_frames.py [OUT.json] | --deliver [OUT.json] | --deliver-trace | --rdma [OUT.json]
-       | --rdma --msg-numel M[,M...] [OUT.json] | --rdma-worker [OUT.json] | --frame-worker [OUT.json]"""
+       | --rdma --msg-numel M[,M...] [OUT.json] | --rdma-worker [OUT.json]
+       | --rdma-worker --msg-numel M[,M...] [OUT.json] | --frame-worker [OUT.json]"""
 import json
 import os
 import statistics
@@ -564,6 +568,102 @@ def main_rdma_worker(out_path=None, rounds=7, W=8, M=1024, reps=10):
     return 0
 
 
+def main_msg_worker(out_path, Ms, rounds=7, W=8, reps=10):
+    """The RDMA worker's completion loop at the message lengths `Ms`, on
+    main_rdma_worker's method (one poll in which every QP accepts a steady-state
+    message; two such polls between one pair of HIP events, the QP state put
+    back, untimed, before each pair): sml_msg_worker_poll with Q = 16384 * 1024
+    // M queue pairs (the same words at every M), and at M = 4096 also a window
+    of Q = 64; beside sml_stream_copy of the poll's algorithmic bytes (20 M
+    bytes a message plus its records) and, at M = 1024, sml_rdma_worker_poll on
+    the same work (pkts_per_msg 4 against 3)."""
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream()
+    arms, meta = {}, {}
+    shapes = [(M, 16384 * 1024 // M) for M in Ms] + ([(4096, 64)] if 4096 in Ms else [])
+    for M, Q in shapes:
+        tag = f"m{M}_q{Q}"
+        x = torch.empty(4 * Q * M, dtype=torch.float32, device=dev).normal_()
+        out = torch.empty_like(x)
+        comps = []
+        for r in range(3):                                   # messages r Q + q: the first batch, then two steady ones
+            c = np.zeros(Q, dtype=np.dtype(sw.rdma_worker.COMPLETION_FIELDS))
+            c["qpn"], c["imm"] = np.arange(Q), ((r * Q + np.arange(Q)) & 0xFFFF) | (3 << 16)
+            comps.append(torch.from_numpy(c.view(np.int64)).to(dev))
+        paths = {"sml_msg_worker": 3, "sml_rdma_worker": 4} if M == 1024 else {"sml_msg_worker": M // 256}
+        for entry, ppm in paths.items():
+            buf = torch.empty(Q * M, dtype=torch.int32, device=dev).random_(-2 ** 31, 2 ** 31 - 1)   # tx is rx
+            wk = sw.RdmaWorker(0, W, Q, M, ppm, dtype=torch.float32, device=dev)
+            assert wk.entry == entry
+            wk.begin(x, out, buf)
+            assert bool((wk.poll(comps[0], buf, buf)[0] == sw.RDMA_WORKER_POSTED).all())
+            snap = wk.state.clone()
+            for r in (1, 2):                                 # checked before anything is timed: both polls post
+                assert bool((wk.poll(comps[r], buf, buf)[0] == sw.RDMA_WORKER_POSTED).all())
+
+            def poll(r, wk=wk, comps=comps, buf=buf):
+                wk.poll(comps[r], buf, buf, stream=st)
+
+            arms[f"{tag}_{entry}_poll"] = (poll, lambda wk=wk, snap=snap: wk.state.copy_(snap))
+        alg = Q * (5 * 4 * M + 8 + 24 + 1 + 2 * 32)
+        half = (alg // 2 + 4095) // 4096 * 4096
+        src = torch.empty(half, dtype=torch.uint8, device=dev).random_(0, 256)
+        dst = torch.empty(half, dtype=torch.uint8, device=dev)
+
+        def copy(r, src=src, dst=dst):
+            sw.stream_copy(src, dst, stream=st)
+
+        arms[tag + "_stream_copy"] = (copy, None)
+        meta[tag] = dict(msg_numel=M, messages_per_call=Q, waves_per_message=(M + 1023) // 1024,
+                         algorithmic_bytes=alg, copy_bytes_moved=2 * half, entries=list(paths))
+
+    def pair(fn, restore):
+        if restore:
+            restore()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(st)
+        fn(1)
+        fn(2)
+        b.record(st)
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / 2 * 1e3
+
+    times = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, (fn, restore) in arms.items():
+            pair(fn, restore)                                                         # warmed
+            times[name].append(statistics.median(pair(fn, restore) for _ in range(reps)))
+    med = {name: statistics.median(v) for name, v in times.items()}
+    res = {name: {"median_us": round(med[name], 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+           for name, v in times.items()}
+    for tag, m in meta.items():
+        for entry in m.pop("entries"):
+            us = med[f"{tag}_{entry}_poll"]
+            res[f"{tag}_{entry}_poll"].update(m, TBps_algorithmic=round(m["algorithmic_bytes"] / us / 1e6, 3),
+                                              ns_per_KiB=round(us * 1e3 / (m["algorithmic_bytes"] / 1024), 4),
+                                              time_over_stream_copy=round(us / med[tag + "_stream_copy"], 3))
+        old = f"{tag}_sml_rdma_worker_poll"
+        if old in med:
+            res[f"{tag}_sml_msg_worker_poll"]["time_over_sml_rdma_worker_poll"] = round(
+                med[f"{tag}_sml_msg_worker_poll"] / med[old], 3)
+        res[tag + "_stream_copy"].update(TBps=round(m["copy_bytes_moved"] / med[tag + "_stream_copy"] / 1e6, 3))
+    text = json.dumps({
+        "what": f"side measurement (not bench.py's headline): sml_msg_worker_poll at msg_numel {Ms}, FLOAT32, W={W}, "
+                f"Q = 16384 * 1024 // msg_numel queue pairs (and Q = 64 at 4096), a slice of 4 Q M elements, tx == rx "
+                f"in device memory; one call = one poll in which every QP accepts a steady-state message; msg_numel "
+                f"1024: sml_rdma_worker_poll (pkts_per_msg 4) on the same work; beside sml_stream_copy of the poll's "
+                f"algorithmic bytes; all arms in one process; a timing = two calls between one pair of HIP events "
+                f"(call time, not kernel time), the QP state restored untimed before each pair, the median of {reps} "
+                f"per round, {rounds} interleaved rounds, medians with the rounds' min-max; the buffers are reused "
+                f"between timings (not cold); nothing here was measured before this file was written",
+        "device": torch.cuda.get_device_name(0), "arms": res}, indent=1)
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main_frame_worker(out_path=None, rounds=7, W=8, P=256, reps=10):
     """The DPDK worker's receive loop (sml_frame_worker_poll: judge, accept) at
     Q = 16384 and Q = 64 tx slots: FLOAT32, a slice of 4 Q P elements, a timed
@@ -679,6 +779,8 @@ def main_frame_worker(out_path=None, rounds=7, W=8, P=256, reps=10):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--frame-worker":
         sys.exit(main_frame_worker(sys.argv[2] if len(sys.argv) > 2 else None))
+    if len(sys.argv) > 3 and sys.argv[1] == "--rdma-worker" and sys.argv[2] == "--msg-numel":
+        sys.exit(main_msg_worker(sys.argv[4] if len(sys.argv) > 4 else None, [int(m) for m in sys.argv[3].split(",")]))
     if len(sys.argv) > 1 and sys.argv[1] == "--rdma-worker":
         sys.exit(main_rdma_worker(sys.argv[2] if len(sys.argv) > 2 else None))
     if len(sys.argv) > 3 and sys.argv[1] == "--rdma" and sys.argv[2] == "--msg-numel":
