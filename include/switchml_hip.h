@@ -858,5 +858,6 @@ uint64_t sml_set_payload_nt_threshold(uint64_t bytes);
 #include "switchml_messages.h"
 #include "switchml_msg_switch.h"
 #include "switchml_msg_worker.h"
+#include "switchml_msg_batch.h"
 
 #endif /* SWITCHML_HIP_H_ */

@@ -55,10 +55,14 @@
  *     sml_switch_aggregate with d_out = NULL (the payload sum knows no block
  *     size: pass any packet size that divides B*M, such as 64) ->
  *     sml_msg_dequantize.
+ *   the batched round trip over the FIFO slices of several jobs:
+ *     sml_msg_roundtrip_loopback_batch (switchml_msg_batch.h), which the
+ *     client's bulk and fused modes reach at general.packet_numel = msg_numel.
  * Not served at msg_numel > 1024 (they keep returning SML_ERR_UNSUPPORTED): the
- * per-packet bursts, the batched round trip, the DPDK frames, sml_rdma_switch
- * and the sml_rdma_worker_* calls themselves (their sml_msg_switch and
- * sml_msg_worker_* twins serve them) and the client's config keys. */
+ * per-packet bursts and the burst server, the DPDK frames, sml_rdma_switch and
+ * the sml_rdma_worker_* calls themselves (their sml_msg_switch and
+ * sml_msg_worker_* twins serve them), sml_roundtrip_loopback_batch_typed
+ * itself, and in the client backend.hip.mode = packet and backend = xgmi. */
 #ifndef SWITCHML_MESSAGES_H_
 #define SWITCHML_MESSAGES_H_
 

@@ -29,6 +29,9 @@ enum DataType { FLOAT32, INT32, FLOAT16, BFLOAT16 };
 inline bool IsHalfType(DataType type) { return type == FLOAT16 || type == BFLOAT16; }
 // Float types are quantized: an exponent per packet, hence the extra batch.
 inline bool IsFloatType(DataType type) { return type == FLOAT32 || IsHalfType(type); }
+// The five packet sizes of the per-packet paths (per-LTU and burst hooks, burst
+// server, the in-node switch); bulk and fused modes take every message size.
+inline bool IsPacketNumel(uint64_t n) { return n == 64 || n == 128 || n == 256 || n == 512 || n == 1024; }
 inline const char* DataTypeName(DataType type) {
     switch (type) {
         case FLOAT32: return "FLOAT32";

@@ -11,6 +11,7 @@
 #include <sstream>
 
 #include "common.h"
+#include "switchml_hip.h"
 
 namespace switchml {
 
@@ -144,6 +145,22 @@ void Config::Validate() {
     }
     const std::string& m = backend_.hip.mode;
     if (m != "bulk" && m != "fused" && m != "packet") throw SwitchMLFatal("backend.hip.mode must be bulk|fused|packet");
+    // general.packet_numel on the HIP pre/post-processor: the dummy backend's
+    // bulk and fused modes take every message size (an LTU may mirror
+    // backend.rdma.msg_numel); the per-packet paths and the in-node switch
+    // the five packet sizes.  Refused here, by name, before any launch.
+    if (g.prepostprocessor != "bypass" && !IsPacketNumel(g.packet_numel)) {
+        const std::string key = "general.packet_numel = " + std::to_string(g.packet_numel);
+        if (g.packet_numel > UINT32_MAX || !sml_msg_numel_supported((uint32_t)g.packet_numel))
+            throw SwitchMLFatal(key + ": the HIP pre/post-processor serves the multiples of 64 up to 16384 "
+                                "(sml_msg_numel_supported)");
+        if (g.backend == "xgmi" || m == "packet")
+            throw SwitchMLFatal(key + " is not supported by " +
+                                (g.backend == "xgmi" ? "backend = xgmi" : "backend.hip.mode = packet (the per-LTU "
+                                 "hooks, the burst hooks and the burst server)") +
+                                ", which serves 64, 128, 256, 512 and 1024; backend = dummy with backend.hip.mode = "
+                                "bulk or fused serves every multiple of 64 up to 16384");
+    }
     const std::string& r = backend_.hip.packet_ring;
     if (r != "device" && r != "pinned" && r != "pageable")
         throw SwitchMLFatal("backend.hip.packet_ring must be device|pinned|pageable");

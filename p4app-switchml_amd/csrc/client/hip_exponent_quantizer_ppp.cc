@@ -11,10 +11,9 @@ HipExponentQuantizerPPP::HipExponentQuantizerPPP(Config& config, WorkerTid worke
     : PrePostProcessor(config, worker_tid, ltu_size, batch_num_ltus), per_ltu_calls_(per_ltu_calls),
       round_flags_(config.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u) {
     ltu_numel_ = ltu_size / 4;
-    if (ltu_size % 4 || !(ltu_numel_ == 64 || ltu_numel_ == 128 || ltu_numel_ == 256 || ltu_numel_ == 512 ||
-                          ltu_numel_ == 1024))
-        throw SwitchMLFatal("hip_exponent_quantizer supports packet_numel 64, 128, 256, 512, 1024; got " +
-                            std::to_string(ltu_numel_));
+    if (ltu_size % 4 || ltu_numel_ > UINT32_MAX || !sml_msg_numel_supported((uint32_t)ltu_numel_))
+        throw SwitchMLFatal("hip_exponent_quantizer supports every packet_numel that sml_msg_numel_supported "
+                            "accepts (a multiple of 64 up to 16384); got " + std::to_string(ltu_numel_));
     hip_ok(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
 }
 
@@ -74,6 +73,18 @@ void HipExponentQuantizerPPP::refuse_half(const char* call) const {
         throw SwitchMLFatal(std::string(call) + ": " + DataTypeName(dt) +
                             " jobs are not supported by the per-LTU and burst hooks (backend.hip.mode = packet) "
                             "without backend.hip.half_packets = true; set it, or backend.hip.mode = bulk or fused");
+}
+
+// An LTU of more than 1024 elements (general.packet_numel = backend.rdma.msg_numel)
+// runs through the bulk hooks and the fused round trip, which take every
+// message size; the per-LTU hooks, the burst hooks and the burst server stay
+// at the five packet sizes and refuse any other by name, before any launch.
+void HipExponentQuantizerPPP::refuse_long_ltu(const char* call) const {
+    if (!IsPacketNumel(ltu_numel_))
+        throw SwitchMLFatal(std::string(call) + ": general.packet_numel = " + std::to_string(ltu_numel_) +
+                            " is not supported by the per-LTU hooks, the burst hooks and the burst server "
+                            "(backend.hip.mode = packet), which serve 64, 128, 256, 512 and 1024; set "
+                            "backend.hip.mode = bulk or fused");
 }
 
 void HipExponentQuantizerPPP::CleanupJobSlice() {
@@ -139,6 +150,7 @@ const int32_t* HipExponentQuantizerPPP::read_packet(const void* buf, size_t byte
 }
 
 void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info) {
+    refuse_long_ltu("PreprocessSingle");
     refuse_half("PreprocessSingle");
     const Tensor& s = job_slice_->slice;
     const uint32_t P = (uint32_t)ltu_numel_;
@@ -182,6 +194,7 @@ void HipExponentQuantizerPPP::preprocess_single(uint64_t ltu_id, void* entries_p
 // words, ltu_size bytes); the caller may reuse a host-memory packet buffer
 // as soon as this returns, so those calls synchronise.
 void HipExponentQuantizerPPP::postprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info) {
+    refuse_long_ltu("PostprocessSingle");
     refuse_half("PostprocessSingle");
     const Tensor& s = job_slice_->slice;
     const uint32_t P = (uint32_t)ltu_numel_;
@@ -239,6 +252,7 @@ void HipExponentQuantizerPPP::burst(BurstKind kind, uint32_t n, const uint64_t* 
         {"ProcessPostprocessReuseBurst", "sml_exchange_burst", SML_BURST_EXCHANGE, sml_exchange_burst_typed},
     };
     const Names& as = kNames[static_cast<int>(kind)];
+    refuse_long_ltu(as.hook);
     refuse_half(as.hook);
     const Tensor& s = job_slice_->slice;
     const bool flt = IsFloatType(s.data_type);
@@ -354,21 +368,21 @@ void HipExponentQuantizerPPP::ProcessPostprocessReuseBurst(uint32_t n, const uin
 void HipExponentQuantizerPPP::ExponentsBulk(void* exps_plane) {
     const Tensor& s = job_slice_->slice;
     if (!IsFloatType(s.data_type)) return;
-    check(sml_exponents_typed(s.in_ptr, SmlFloatType(s.data_type), s.numel, (uint32_t)ltu_numel_,
-                              static_cast<int8_t*>(exps_plane), stream_),
-          "sml_exponents");
+    check(sml_msg_exponents(s.in_ptr, SmlFloatType(s.data_type), s.numel, (uint32_t)ltu_numel_,
+                            static_cast<int8_t*>(exps_plane), stream_),
+          "sml_msg_exponents");
 }
 
 void HipExponentQuantizerPPP::PreprocessBulk(void* payload_plane, void* exps_plane, const void* global_exps,
                                              bool payload_le) {
     const Tensor& s = job_slice_->slice;
-    if (IsFloatType(s.data_type)) {   // FLOAT32 forwards to sml_quantize_pack
-        check(sml_quantize_pack_typed(s.in_ptr, SmlFloatType(s.data_type), s.numel, (uint32_t)ltu_numel_,
-                                      config_.general_.num_workers, static_cast<const int8_t*>(global_exps),
-                                      static_cast<int32_t*>(payload_plane),
-                                      global_exps ? nullptr : static_cast<int8_t*>(exps_plane),
-                                      (payload_le ? SML_FLAG_PAYLOAD_LE : 0u) | round_flags_, stream_),
-              "sml_quantize_pack");
+    if (IsFloatType(s.data_type)) {   // a packet size forwards to sml_quantize_pack_typed
+        check(sml_msg_quantize_pack(s.in_ptr, SmlFloatType(s.data_type), s.numel, (uint32_t)ltu_numel_,
+                                    config_.general_.num_workers, static_cast<const int8_t*>(global_exps),
+                                    static_cast<int32_t*>(payload_plane),
+                                    global_exps ? nullptr : static_cast<int8_t*>(exps_plane),
+                                    (payload_le ? SML_FLAG_PAYLOAD_LE : 0u) | round_flags_, stream_),
+              "sml_msg_quantize_pack");
     } else {
         if (payload_le)
             hip_ok(hipMemcpyAsync(payload_plane, s.in_ptr, s.numel * 4, hipMemcpyDeviceToDevice, stream_),
@@ -382,11 +396,11 @@ void HipExponentQuantizerPPP::PreprocessBulk(void* payload_plane, void* exps_pla
 
 void HipExponentQuantizerPPP::PostprocessBulk(const void* payload_plane, const void* global_exps, bool payload_le) {
     const Tensor& s = job_slice_->slice;
-    if (IsFloatType(s.data_type)) {   // FLOAT32 forwards to sml_dequantize
-        check(sml_dequantize_typed(static_cast<const int32_t*>(payload_plane), static_cast<const int8_t*>(global_exps),
-                                   s.numel, (uint32_t)ltu_numel_, config_.general_.num_workers, s.out_ptr,
-                                   SmlFloatType(s.data_type), payload_le ? SML_FLAG_PAYLOAD_LE : 0u, stream_),
-              "sml_dequantize");
+    if (IsFloatType(s.data_type)) {   // a packet size forwards to sml_dequantize_typed
+        check(sml_msg_dequantize(static_cast<const int32_t*>(payload_plane), static_cast<const int8_t*>(global_exps),
+                                 s.numel, (uint32_t)ltu_numel_, config_.general_.num_workers, s.out_ptr,
+                                 SmlFloatType(s.data_type), payload_le ? SML_FLAG_PAYLOAD_LE : 0u, stream_),
+              "sml_msg_dequantize");
     } else {
         if (payload_le)
             hip_ok(hipMemcpyAsync(s.out_ptr, payload_plane, s.numel * 4, hipMemcpyDeviceToDevice, stream_),

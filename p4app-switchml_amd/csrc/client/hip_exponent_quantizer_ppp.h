@@ -82,6 +82,7 @@ class HipExponentQuantizerPPP : public PrePostProcessor {
   private:
     void check(int status, const char* what) const;
     void refuse_per_ltu(const char* call) const;
+    void refuse_long_ltu(const char* call) const;   // throws for an LTU that is not one of the five packet sizes
     void refuse_half(const char* call) const;   // throws for a FLOAT16 / BFLOAT16 slice without backend.hip.half_packets
     void preprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);
     void postprocess_single(uint64_t ltu_id, void* entries_ptr, void* extra_info);

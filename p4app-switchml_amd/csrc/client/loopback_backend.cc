@@ -211,11 +211,11 @@ uint64_t run_slice(PrePostProcessor& base, const Config& cfg, WorkerState& ws, J
     } else if (mode == "packet") {
         run_packet_loop(*ppp, cfg, ws, ppp->NeedsExtraBatch());
     } else if (mode == "fused" && is_float && cfg.backend_.dummy.process_packets) {
-        // FLOAT32 forwards to sml_roundtrip_loopback
-        sml_ok(sml_roundtrip_loopback_typed(staged.slice.in_ptr, staged.slice.out_ptr, SmlFloatType(t.data_type),
-                                            t.numel, (uint32_t)P, W, nullptr, nullptr,
-                                            cfg.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u, st),
-               "sml_roundtrip_loopback");
+        // a packet size forwards to sml_roundtrip_loopback_typed
+        sml_ok(sml_msg_roundtrip_loopback(staged.slice.in_ptr, staged.slice.out_ptr, SmlFloatType(t.data_type),
+                                          t.numel, (uint32_t)P, W, nullptr, nullptr,
+                                          cfg.backend_.hip.vcl ? SML_FLAG_ROUND_RNE : 0u, st),
+               "sml_msg_roundtrip_loopback");
     } else {  // bulk
         void* payload = ws.payload.get(B * P * 4, st);
         void* exps = ws.exps.get(B, st);
@@ -399,10 +399,10 @@ void ExecutePlan(const BatchPlan& plan, Round& r, Context& ctx, const Config& cf
                     table.push_back(sml_typed_slice{sl.in, sl.out, sl.numel, (uint32_t)sl.data_type, 0u});
                 }
                 ctx.GetStats().AddBatchCall(table.size());
-                sml_ok(sml_roundtrip_loopback_batch_typed(table.data(), (uint32_t)table.size(),
-                                                          (uint32_t)cfg.general_.packet_numel,
-                                                          cfg.general_.num_workers, rne, ppp.stream()),
-                       "sml_roundtrip_loopback_batch_typed");
+                sml_ok(sml_msg_roundtrip_loopback_batch(table.data(), (uint32_t)table.size(),
+                                                        (uint32_t)cfg.general_.packet_numel,
+                                                        cfg.general_.num_workers, rne, ppp.stream()),
+                       "sml_msg_roundtrip_loopback_batch");
             } else {   // INT32 and pageable-host slices
                 PlanPiece& pc = r.pieces[s.first];
                 JobSlice js = SliceOf(r, pc);
@@ -448,7 +448,7 @@ bool LoopbackBackend::BatchEligible() const {
 // of every job (dummy_worker_thread.cc:73-177) because a CPU core is the unit
 // of parallelism; on the GPU one launch already fills the chip, so here ONE
 // thread takes the queued jobs whole and runs every slice of up to
-// batch_jobs of them in one sml_roundtrip_loopback_batch_typed call — the
+// batch_jobs of them in one sml_msg_roundtrip_loopback_batch call — the
 // same slice geometry (so the same bits) with one launch per element type
 // present (FLOAT32, FLOAT16, BFLOAT16) and one event per batch instead of
 // num_worker_threads launches per job.  Jobs whose buffers overlap an

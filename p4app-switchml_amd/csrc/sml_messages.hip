@@ -37,6 +37,9 @@
 // and a 16-byte vector never straddles two.  The message of a chunk comes from
 // two multiplications with host-computed reciprocals (msg_magic), exact for
 // every numel < 2^56: no division in the kernel.
+//
+// The batched round trip (k_msg_roundtrip_batch, switchml_msg_batch.h) is the
+// fused round trip's geometry over the slices of a table of kernel arguments.
 #include "sml_host.h"
 #include "sml_msg_deal.h"
 #include "switchml_messages.h"
@@ -192,8 +195,100 @@ __global__ __launch_bounds__(kMsgMaxWaves * kWave) void k_msg_quantize(MsgArgs<t
     }
 }
 
+// The fused round trip over a batch of slices (of one or several jobs) in ONE
+// launch (include/switchml_msg_batch.h).  The batch's message groups are
+// numbered consecutively over the slices: slice s owns ceil(B_s / per_group)
+// groups, group_end[s] = groups of slices 0..s, so a group never spans two
+// slices and a slice's messages restart at its own first element.  The table
+// travels as kernel arguments, 1816 bytes for every T.
+template <class T>
+struct MsgBatchArgs {
+    const T* in[SML_MAX_BATCH_SLICES];
+    T* out[SML_MAX_BATCH_SLICES];
+    uint64_t numel[SML_MAX_BATCH_SLICES];
+    uint32_t group_end[SML_MAX_BATCH_SLICES];
+    uint32_t nslices;
+    uint32_t M;
+    uint32_t wpm;
+    uint32_t per_group;
+    uint32_t W;
+    uint32_t xcd;
+};
+static_assert(sizeof(MsgBatchArgs<float>) <= 4096 && sizeof(MsgBatchArgs<uint16_t>) == sizeof(MsgBatchArgs<float>),
+              "the table travels as kernel arguments");
+
+// The slice of message group g as the single-slice kernel's arguments, and the
+// group's first message inside that slice.  g is workgroup-uniform: the search
+// over group_end is scalar loads and scalar branches.  No division: nmsgs is
+// not the slice's count but a bound that answers "is message k live" for the
+// messages of this group alone, from k * M < numel.  A slice whose count is no
+// multiple of per_group ends in a group with dead messages, whose waves take
+// msg_compute's barrier and store nothing.
+template <class T>
+__device__ __forceinline__ uint64_t msg_batch_group(const MsgBatchArgs<T>& b, uint32_t g, MsgArgs<T>& a) {
+    uint32_t lo = 0, hi = b.nslices - 1;                 // first s with group_end[s] > g
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (b.group_end[mid] > g) hi = mid;
+        else lo = mid + 1;
+    }
+    const uint64_t k0 = (uint64_t)(g - (lo ? b.group_end[lo - 1] : 0u)) * b.per_group;
+    a.in = b.in[lo];
+    a.out = b.out[lo];
+    a.numel = b.numel[lo];
+    a.nmsgs = k0 + 1;                                    // a group exists for its first message
+    for (uint32_t j = 1; j < b.per_group; j++) a.nmsgs += (k0 + j) * b.M < a.numel;
+    a.ngroups = 0;
+    a.gexp = nullptr;
+    a.payload = nullptr;
+    a.exps_out = nullptr;
+    a.M = b.M;
+    a.wpm = b.wpm;
+    a.per_group = b.per_group;
+    a.W = b.W;
+    a.xcd = b.xcd;
+    return k0;
+}
+
+// k_msg_quantize's round trip with the slice looked up once per loop trip.
+// The next group may belong to the next slice: its lookup comes before its
+// loads, the loaded registers travel with their own slice's arguments (nxt
+// becomes cur), and the stores use the slice the loads came from.  A lane
+// stores exactly the elements it loaded, after their loads, and slices do not
+// overlap, so in == out within a slice is safe.
+template <class E, bool RNE, bool NT>
+__global__ __launch_bounds__(kMsgMaxWaves * kWave) void k_msg_roundtrip_batch(MsgBatchArgs<typename E::raw> b) {
+    __shared__ float lut[256];
+    __shared__ uint32_t smax[2][kMsgMaxWaves];
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = wave_index();
+    const uint32_t part = b.per_group == 1 ? wave : wave & (b.wpm - 1);
+    const uint32_t sub = b.per_group == 1 ? 0u : wave >> (b.wpm - 1);
+    const uint64_t ngroups = b.group_end[b.nslices - 1];
+    uint64_t g = xcd_block(b.xcd);
+    MsgArgs<typename E::raw> cur, nxt;
+    uint64_t k = 0, kn = 0;
+    f4 v[kMsgU];
+    if (g < ngroups) {
+        k = msg_batch_group(b, (uint32_t)g, cur) + sub;
+        msg_load<E>(cur, k, part, lane, v);
+    }
+    msg_build_lut(lut, b.W);
+    for (uint32_t trip = 0; g < ngroups; trip ^= 1u) {
+        g += gridDim.x;
+        const bool more = g < ngroups;
+        if (more) kn = msg_batch_group(b, (uint32_t)g, nxt) + sub;
+        msg_compute<E, false, true, RNE, false, true, NT>(cur, k, wave, part, lane, v, lut, smax[trip]);
+        if (more) {
+            msg_load<E>(nxt, kn, part, lane, v);
+            cur = nxt;
+            k = kn;
+        }
+    }
+}
+
 // floor(c / d) for chunks of 64 elements, d = M / 64 in 1..256, without a
-// division in the kernel.  hi = ceil(2^64 / d) (0 for d == 1, which needs
+// division in the kernel. hi = ceil(2^64 / d) (0 for d == 1, which needs
 // none): mulhi(c, hi) = floor(c / d) while c * (hi * d - 2^64) < 2^64, and
 // hi * d - 2^64 < d <= 2^8, so for every c < 2^56.  lo = ceil(2^20 / d):
 // (r * lo) >> 20 = floor(r / d) while r * (lo * d - 2^20) < 2^20, r < 2^12.
@@ -304,19 +399,27 @@ using MsgHalf = Elem16<F16 ? kHalfF16 : kHalfBF16>;
 
 // Geometry of a launch: message groups, the one-shot grid, and XCD runs of the
 // plane kernels' byte length (g_xcd_chunk workgroups of 4 tiles of 4 KiB).
-template <class T>
-static uint32_t msg_geometry(MsgArgs<T>& a) {
-    a.wpm = (a.M + kTileElems - 1) / kTileElems;
-    a.per_group = a.wpm <= 2 ? kWavesPerBlock / a.wpm : 1;
-    a.ngroups = (a.nmsgs + a.per_group - 1) / a.per_group;
+// (A is MsgArgs, or MsgBatchArgs with its group count.)
+template <class A>
+static uint32_t msg_grid(A& a, uint64_t ngroups) {
     const uint64_t run = (uint64_t)g_xcd_chunk.load(std::memory_order_relaxed) * 4 * kTileElems;
     const uint64_t c = run / ((uint64_t)a.per_group * a.M);
     a.xcd = run == 0 ? 0u : (uint32_t)(c ? c : 1);
-    uint64_t g = a.ngroups;
+    uint64_t g = ngroups;
     const uint32_t lim = g_grid_limit.load(std::memory_order_relaxed);
     if (lim && g > lim) g = lim;
     if (g > 0x7fffffffull) g = 0x7fffffffull;
     return (uint32_t)g;
+}
+
+inline uint32_t msg_per_group(uint32_t wpm) { return wpm <= 2 ? kWavesPerBlock / wpm : 1; }
+
+template <class T>
+static uint32_t msg_geometry(MsgArgs<T>& a) {
+    a.wpm = msg_waves(a.M);
+    a.per_group = msg_per_group(a.wpm);
+    a.ngroups = (a.nmsgs + a.per_group - 1) / a.per_group;
+    return msg_grid(a, a.ngroups);
 }
 
 // K1 / K2 / K3 and the round trip (d_out != nullptr) of one typed slice; the
@@ -403,6 +506,45 @@ static sml_status_t msg_quantize_any(const void* d_in, void* d_out, sml_data_typ
                                numel, M, W, d_gexp, d_payload, d_exps_out, flags, stream);
 }
 
+// One non-empty, checked slice into the table of its element type; false when
+// the launch would number more than 2^32 - 1 groups.
+template <class T>
+static bool msg_batch_add(MsgBatchArgs<T>& a, uint64_t& groups, const sml_typed_slice& sl) {
+    const uint64_t nmsgs = sl.numel / a.M + (sl.numel % a.M != 0);
+    groups += (nmsgs + a.per_group - 1) / a.per_group;
+    if (groups > 0xFFFFFFFFull) return false;
+    a.in[a.nslices] = static_cast<const T*>(sl.in);
+    a.out[a.nslices] = static_cast<T*>(sl.out);
+    a.numel[a.nslices] = sl.numel;
+    a.group_end[a.nslices] = (uint32_t)groups;
+    a.nslices++;
+    return true;
+}
+
+// The launch of one type's filled table: nothing for an empty one, the
+// single-slice kernel for one slice, else one k_msg_roundtrip_batch.  fp32
+// takes the unaligned form whatever the slices' starts (FIFO slices start
+// anywhere), as the packet batch does.
+template <template <bool> class EV, class T>
+static sml_status_t msg_batch_launch(MsgBatchArgs<T>& a, bool variant, sml_data_type_t dt, bool rne, bool nt,
+                                     void* stream) {
+    if (a.nslices == 0) return SML_OK;
+    if (a.nslices == 1)
+        return msg_quantize_any(a.in[0], a.out[0], dt, a.numel[0], a.M, (uint16_t)a.W, nullptr, nullptr, nullptr,
+                                rne ? SML_FLAG_ROUND_RNE : 0u, stream);
+    const dim3 grid(msg_grid(a, a.group_end[a.nslices - 1]));
+    const uint32_t threads = a.wpm * a.per_group * kWave;
+    hipStream_t st = (hipStream_t)stream;
+    dispatch_bools([&](auto V, auto RNE, auto NT) {
+        k_msg_roundtrip_batch<EV<V()>, RNE(), NT()><<<grid, threads, 0, st>>>(a);
+    }, variant, rne, nt);
+    return launch_check();
+}
+
+// fp32 slices of a batch: always the 4-byte-aligned form.
+template <bool>
+using MsgBatchF32 = ElemF32<false>;
+
 }  // namespace sml
 
 using namespace sml;
@@ -471,6 +613,43 @@ sml_status_t sml_msg_roundtrip_loopback(const void* d_in, void* d_out, sml_data_
                                             flags, stream);
     return msg_quantize_any(d_in, d_out, dt, numel, msg_numel, num_workers, nullptr, d_payload, d_exps_out, flags,
                             stream);
+}
+
+sml_status_t sml_msg_roundtrip_loopback_batch(const sml_typed_slice* slices, uint32_t num_slices, uint32_t msg_numel,
+                                              uint16_t num_workers, uint32_t flags, void* stream) {
+    if (!msg_supported(msg_numel)) return SML_ERR_UNSUPPORTED;
+    if (num_workers == 0 || num_slices > SML_MAX_BATCH_SLICES || (num_slices && !slices)) return SML_ERR_INVALID_ARG;
+    // One table per element type, every slice checked before any launch.
+    MsgBatchArgs<float> f32;
+    MsgBatchArgs<uint16_t> h[2];   // [0] BFLOAT16, [1] FLOAT16
+    f32.nslices = h[0].nslices = h[1].nslices = 0;
+    f32.M = h[0].M = h[1].M = msg_numel;
+    f32.wpm = h[0].wpm = h[1].wpm = msg_waves(msg_numel);
+    f32.per_group = h[0].per_group = h[1].per_group = msg_per_group(f32.wpm);
+    f32.W = h[0].W = h[1].W = num_workers;
+    uint64_t groups_f32 = 0, groups_h[2] = {0, 0}, out_bytes = 0;
+    for (uint32_t i = 0; i < num_slices; i++) {
+        const sml_typed_slice& sl = slices[i];
+        if (sl.reserved != 0) return SML_ERR_INVALID_ARG;
+        const sml_data_type_t dt = (sml_data_type_t)sl.data_type;
+        if (!msg_float_type(dt) || sl.numel >= kMsgNumelLimit) return SML_ERR_UNSUPPORTED;
+        if (sl.numel == 0) continue;
+        if (!msg_elem_ok(sl.in, dt) || !msg_elem_ok(sl.out, dt)) return SML_ERR_INVALID_ARG;
+        const int k = dt == SML_FLOAT16;
+        if (!(dt == SML_FLOAT32 ? msg_batch_add(f32, groups_f32, sl) : msg_batch_add(h[k], groups_h[k], sl)))
+            return SML_ERR_UNSUPPORTED;
+        out_bytes += (dt == SML_FLOAT32 ? 4 : 2) * sl.numel;
+    }
+    if (f32.nslices + h[0].nslices + h[1].nslices == 0) return SML_OK;
+    // the packet sizes sml_msg_roundtrip_loopback hands over: the packet batch
+    if (msg_is_packet(msg_numel))
+        return sml_roundtrip_loopback_batch_typed(slices, num_slices, msg_numel, num_workers, flags, stream);
+    // the outputs of the whole call past the Infinity Cache: non-temporal stores
+    const bool rne = flags & SML_FLAG_ROUND_RNE, nt = nt_from(out_bytes);
+    sml_status_t s = msg_batch_launch<MsgBatchF32>(f32, false, SML_FLOAT32, rne, nt, stream);
+    for (int k = 0; k < 2 && s == SML_OK; k++)
+        s = msg_batch_launch<MsgHalf>(h[k], k == 1, k ? SML_FLOAT16 : SML_BFLOAT16, rne, nt, stream);
+    return s;
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@ from .frames import (RxSlice, RxSliceInt32, dequantize_frames, frame_bytes, fram
 from .knobs import (debug_stall, set_grid_limit, set_payload_nt_threshold, set_quantize_tile_slices,
                     set_stream_tile_slices, set_xcd_chunk, stream_copy)
 from .messages import (msg_dequantize, msg_exponents, msg_numel_supported, msg_quantize_pack,
-                       msg_roundtrip_loopback)
+                       msg_roundtrip_loopback, msg_roundtrip_loopback_batch)
 from .packets import BurstServer, exchange_burst, packet_burst, postprocess_burst, preprocess_burst
 from .planes import (bswap_i32, dequantize, exponents, fifo_slice, loopback_aggregate, num_blocks, quantize_pack,
                      quantize_pack_launcher, roundtrip_loopback, roundtrip_loopback_batch, scale_lut,

@@ -24,6 +24,7 @@ FRAME_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_frame_worker.h")  # 
 MESSAGES_HEADER_PATH = os.path.join(_INCLUDE, "switchml_messages.h")          # included by switchml_hip.h
 MSG_SWITCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_msg_switch.h")      # included by switchml_hip.h
 MSG_WORKER_HEADER_PATH = os.path.join(_INCLUDE, "switchml_msg_worker.h")      # included by switchml_hip.h
+MSG_BATCH_HEADER_PATH = os.path.join(_INCLUDE, "switchml_msg_batch.h")        # included by switchml_hip.h
 
 # sml_status_t
 SML_OK, SML_ERR_INVALID_ARG, SML_ERR_UNSUPPORTED, SML_ERR_ALIGNMENT, SML_ERR_HIP = range(5)
@@ -264,6 +265,12 @@ MSG_SWITCH_SIGNATURES = {
 MSG_WORKER_SIGNATURES = {name.replace("sml_rdma_worker", "sml_msg_worker"): sig
                          for name, sig in RDMA_WORKER_SIGNATURES.items()}
 
+# include/switchml_msg_batch.h, likewise (tests/test_msg_batch_cpu.py): the typed batch's call for
+# messages of any supported length
+MSG_BATCH_SIGNATURES = {
+    "sml_msg_roundtrip_loopback_batch": SIGNATURES["sml_roundtrip_loopback_batch_typed"],
+}
+
 _lib = None
 
 
@@ -278,7 +285,8 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **RDMA_SWITCH_SIGNATURES, **RDMA_WORKER_SIGNATURES,
                                       **FRAME_WORKER_SIGNATURES, **MESSAGES_SIGNATURES,
-                                      **MSG_SWITCH_SIGNATURES, **MSG_WORKER_SIGNATURES}.items():
+                                      **MSG_SWITCH_SIGNATURES, **MSG_WORKER_SIGNATURES,
+                                      **MSG_BATCH_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from .abi import MSG_NUMEL_MAX, MSG_NUMEL_STEP, call, lib
 from .glue import _dev, _float_type, _opt, _stream, _torch
+from .planes import typed_slice_table
 
 
 def msg_numel_supported(msg_numel: int) -> bool:
@@ -66,3 +67,11 @@ def msg_roundtrip_loopback(x, msg_numel: int, num_workers: int = 1, out=None, pa
          x.numel(), msg_numel, num_workers, _opt(payload, torch.int32, "payload"),
          _opt(exps_out, torch.int8, "exps_out"), flags, _stream(stream, x))
     return out
+
+
+def msg_roundtrip_loopback_batch(slices, msg_numel: int, num_workers: int = 1, flags: int = 0, stream=None):
+    """planes.roundtrip_loopback_batch with msg_numel in place of packet_numel
+    (include/switchml_msg_batch.h): `slices` is a list of (x, out) tensor
+    pairs, and slice i gets exactly msg_roundtrip_loopback(x_i, out=out_i)."""
+    arr, st = typed_slice_table(slices, stream)
+    call("sml_msg_roundtrip_loopback_batch", arr, len(slices), msg_numel, num_workers, flags, st)

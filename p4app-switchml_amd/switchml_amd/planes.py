@@ -145,14 +145,10 @@ def roundtrip_loopback(x, packet_numel: int = 256, num_workers: int = 1, out=Non
     return out
 
 
-def roundtrip_loopback_batch(slices, packet_numel: int = 256, num_workers: int = 1, flags: int = 0, stream=None):
-    """The fused round trip over several slices in one call: `slices` is a
-    list of (x, out) device (or pinned host) tensor pairs, fp32, fp16 or bf16
-    (a pair's two dtypes equal, the pairs' dtypes free); slice i gets exactly
-    roundtrip_loopback(x_i, out=out_i) — its blocks start at its own first
-    element.  The list goes whole through sml_roundtrip_loopback_batch_typed:
-    one launch per dtype present (an all-fp32 list: the one launch of
-    sml_roundtrip_loopback_batch)."""
+def typed_slice_table(slices, stream=None):
+    """(sml_typed_slice array, stream) of a list of (x, out) tensor pairs: the
+    table of sml_roundtrip_loopback_batch_typed and of
+    sml_msg_roundtrip_loopback_batch."""
     for x, o in slices:
         if x.numel() != o.numel():
             raise ValueError("slice in/out sizes differ")
@@ -163,4 +159,16 @@ def roundtrip_loopback_batch(slices, packet_numel: int = 256, num_workers: int =
     for i, (x, o) in enumerate(slices):
         dt = _float_type(getattr(x, "dtype", None), "x")
         arr[i] = TypedSlice(_dev(x, x.dtype, "x").value, _dev(o, x.dtype, "out").value, x.numel(), dt, 0)
+    return arr, st
+
+
+def roundtrip_loopback_batch(slices, packet_numel: int = 256, num_workers: int = 1, flags: int = 0, stream=None):
+    """The fused round trip over several slices in one call: `slices` is a
+    list of (x, out) device (or pinned host) tensor pairs, fp32, fp16 or bf16
+    (a pair's two dtypes equal, the pairs' dtypes free); slice i gets exactly
+    roundtrip_loopback(x_i, out=out_i) — its blocks start at its own first
+    element.  The list goes whole through sml_roundtrip_loopback_batch_typed:
+    one launch per dtype present (an all-fp32 list: the one launch of
+    sml_roundtrip_loopback_batch)."""
+    arr, st = typed_slice_table(slices, stream)
     call("sml_roundtrip_loopback_batch_typed", arr, len(slices), packet_numel, num_workers, flags, st)

@@ -14,7 +14,15 @@ own spread over the rounds, (max - min) / median, says what a difference means.
 Before anything is timed, at the timed size: M = 1024 through the new entry
 points equals the packet kernels bit for bit, and for every M the fused round
 trip equals K1 then K4.
+The batched round trip (sml_msg_roundtrip_loopback_batch), per M of BATCH_MS: 64
+fp32 slices that together cover the stream, in one call (batch), against the
+same 64 slices as 64 sml_msg_roundtrip_loopback launches (loop) and against
+rt_M, one launch over the whole stream (the floor); the three share buffers and
+rounds.  The tables and the per-slice arguments are built before the timing, so
+an arm's host side is its C calls.  Before the timing: batch equals loop bit
+for bit.
 Usage: bench_long_messages.py [OUT.json]"""
+import ctypes
 import json
 import os
 import statistics
@@ -27,6 +35,8 @@ import torch  # noqa: E402
 import switchml_amd as sw  # noqa: E402
 
 MS = (1024, 2048, 2304, 4096, 16384, 768)
+BATCH_MS = (2304, 4096, 16384)
+NSLICES = 64
 
 
 def main(N=64 << 20, nbuf=4, rounds=9, reps=20, W=1):
@@ -57,6 +67,21 @@ def main(N=64 << 20, nbuf=4, rounds=9, reps=20, W=1):
             sw.msg_roundtrip_loopback(xs[k], M, W, out=outs[k], stream=st)
         return {f"k1_M{M}": k1, f"k4_M{M}": k4, f"rt_M{M}": rt}
 
+    # the stream cut into NSLICES slices at multiples of 64 elements (no multiple of any M of BATCH_MS)
+    cuts = [N * i // NSLICES // 64 * 64 + (64 if 0 < i < NSLICES else 0) for i in range(NSLICES + 1)]
+    tables = [sw.planes.typed_slice_table([(xs[k][a:b], outs[k][a:b]) for a, b in zip(cuts, cuts[1:])], st)[0]
+              for k in range(nbuf)]
+    L, sp = sw.abi.lib(), ctypes.c_void_p(st.cuda_stream)
+
+    def batch_arms(M):
+        def batch(k):
+            sw.abi.call("sml_msg_roundtrip_loopback_batch", tables[k], NSLICES, M, W, 0, sp)
+
+        def loop(k):
+            for s in tables[k]:
+                L.sml_msg_roundtrip_loopback(s.in_, s.out, sw.abi.FLOAT32, s.numel, M, W, None, None, 0, sp)
+        return {f"batch_M{M}": batch, f"loop_M{M}": loop}
+
     def base_k1(k):
         p, e = views(1024, k)
         sw.quantize_pack(xs[k], 1024, W, payload=p, exps_out=e, stream=st)
@@ -86,9 +111,19 @@ def main(N=64 << 20, nbuf=4, rounds=9, reps=20, W=1):
             assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), "M=1024 != the packet kernels"
             assert torch.equal(chain.view(torch.int32), want_out.view(torch.int32)), "M=1024 K4 != the packet K4"
 
+    for M in BATCH_MS:
+        b = batch_arms(M)
+        b[f"loop_M{M}"](0)
+        want_out = outs[0].clone()
+        b[f"batch_M{M}"](0)
+        torch.cuda.synchronize()
+        assert torch.equal(want_out.view(torch.int32), outs[0].view(torch.int32)), f"M={M}: batch != per-slice launches"
+
     arms = {"base_k1": base_k1, "base_k4": base_k4, "base_rt": base_rt, "copy": copy}
     for M in MS:
         arms.update(msg_arms(M))
+    for M in BATCH_MS:
+        arms.update(batch_arms(M))
     for k in range(nbuf):                         # planes for the K4 arms, whichever arm ran last
         base_k1(k)
     times = {name: [] for name in arms}
@@ -120,10 +155,19 @@ def main(N=64 << 20, nbuf=4, rounds=9, reps=20, W=1):
         rows[str(M)] = {k: {"time_over_P1024": round(med[f"{k}_M{M}"] / med[f"base_{k}"], 4),
                             "baseline_spread": round(spread[f"base_{k}"], 4),
                             "time_over_stream_copy": round(med[f"{k}_M{M}"] / med["copy"], 4)} for k in ("k1", "k4", "rt")}
+    # batch and loop over the floor rt_M, whose own spread over the rounds says what a difference means
+    batch_rows = {str(M): {"batch_us": res[f"batch_M{M}"]["median_us"], "loop_us": res[f"loop_M{M}"]["median_us"],
+                           "one_launch_us": res[f"rt_M{M}"]["median_us"],
+                           "batch_over_loop": round(med[f"batch_M{M}"] / med[f"loop_M{M}"], 4),
+                           "batch_over_one_launch": round(med[f"batch_M{M}"] / med[f"rt_M{M}"], 4),
+                           "batch_spread": round(spread[f"batch_M{M}"], 4),
+                           "loop_spread": round(spread[f"loop_M{M}"], 4),
+                           "one_launch_spread": round(spread[f"rt_M{M}"], 4)} for M in BATCH_MS}
     out = {"what": f"side measurement (not bench.py's headline): long RDMA messages, fp32, {N >> 20} Mi elements, "
                    f"W={W}, {nbuf} cycled buckets (cold), {rounds} interleaved rounds x {reps} launches after one "
                    "dropped round, medians, HIP events; spread = (max - min) / median over the rounds",
-           "device": torch.cuda.get_device_name(0), "arms": res, "rows_by_msg_numel": rows}
+           "device": torch.cuda.get_device_name(0), "arms": res, "rows_by_msg_numel": rows,
+           "batch_of_64_slices_by_msg_numel": batch_rows}
     text = json.dumps(out, indent=1)
     print(text)
     if len(sys.argv) > 1:
